@@ -9,8 +9,18 @@ timed region is config 2's virtual steps 2,000-10,000: past the ~1,200-step
 ramp while clusters desynchronise, and ending at the config's 10,000 steps.
 Inputs (cluster state, mailboxes) are resident in HBM before the timed region.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5]
+  python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5] [--full] [--dump-outputs DIR]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
+
+A plain run sets up, warms up, times the K steps and prints one JSON line
+(value, ms_per_step, the kernel's time split and roofline figures, which come
+from counters the timed steps already keep).  --full adds the legs that take
+runs of their own: the CPU-oracle baseline over the same window with its
+parity sample of the GPU's clusters, and the per-rank state digests (at N=1,
+seven more small simulations).  --dump-outputs DIR writes what the last timed
+step left - the statistics and a fixed sample of replica states - as
+DIR/<name>.npy (dump_outputs); the inputs are seeded, so two builds can be
+compared file for file.
 
 --config 3 (ABD + linearizability scan), 4 (FGrid 3x3, leader crash at the
 first timed step, re-election at zone 2) and 5 (WPaxos) print their own lines.
@@ -303,6 +313,47 @@ def cpu_baseline(args, sim=None, min_s=3.0):
     return res
 
 
+DUMP_BLOCK = 256            # --dump-outputs samples whole blocks of this many clusters
+DUMP_BLOCKS = 32
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(sim, path):
+    """What a caller of the timed path (Simulation.step) receives after the last
+    timed step, as float64 .npy files under `path`:
+
+      stats.npy          paxisim_stats_get: the Stats record's uint64 counters, in field order
+      clusters.npy       the local cluster ids sampled below
+      replica_state.npy  paxisim_read_state of those clusters, [cluster, replica, word]: each
+                         replica's ReplicaState record as its little-endian uint32 words
+                         (a uint64 field is two words), so every value is exact in float64
+
+    The sample is fixed: every cluster when they fit, else DUMP_BLOCKS blocks of DUMP_BLOCK
+    clusters drawn with DUMP_SEED; the simulation is seeded, so two runs with the same
+    arguments write equal files."""
+    import ctypes
+    import numpy as np
+    from paxi_amd import abi
+    os.makedirs(path, exist_ok=True)
+    C, N = sim.cfg.clusters, sim.N
+    words = ctypes.sizeof(abi.ReplicaState) // 4
+    nblocks = (C + DUMP_BLOCK - 1) // DUMP_BLOCK
+    keep = min(DUMP_BLOCKS, (DUMP_MAX_BYTES - (1 << 20)) // (DUMP_BLOCK * N * words * 8))
+    blocks = np.arange(nblocks)
+    if nblocks > keep:
+        blocks = np.sort(np.random.RandomState(DUMP_SEED).choice(nblocks, keep, replace=False))
+    ids, recs = [], []
+    for b in blocks:
+        lo = int(b) * DUMP_BLOCK
+        n = min(DUMP_BLOCK, C - lo)
+        ids.append(np.arange(lo, lo + n))
+        recs.append(np.frombuffer(bytes(sim.read_state(lo, n)), dtype="<u4").reshape(n, N, words))
+    np.save(os.path.join(path, "stats.npy"), np.frombuffer(bytes(sim.stats()), dtype="<u8").astype(np.float64))
+    np.save(os.path.join(path, "clusters.npy"), np.concatenate(ids).astype(np.float64))
+    np.save(os.path.join(path, "replica_state.npy"), np.concatenate(recs).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -320,10 +371,18 @@ def main():
                     help="config 4: step of the leader crash (default: the first timed step)")
     ap.add_argument("--kv", type=int, default=1, choices=[0, 1],
                     help="replicas execute into a Database (db.go Execute) - the reference always does")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs the headline figure does not need: the CPU-oracle "
+                         "baseline with its parity sample, and the per-rank state digests")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left (statistics, a fixed sample of replica states) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-shard-check", action="store_true",
-                    help="skip the per-rank state digests (sharding invariance, SURVEY 8e)")
+                    help="with --full: skip the per-rank state digests (sharding invariance, SURVEY 8e)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_shard_check = True
     for k, v in DEFAULTS[args.config].items():
         if getattr(args, k) is None:
             setattr(args, k, v)
@@ -384,6 +443,8 @@ def main():
     kms, launches = sim.kernel_time()
     s1 = sim.stats().as_dict()
     d = stats_delta(s0, s1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sim, args.dump_outputs)
     violations = sim.check()
     lin = None
     if args.config == 3:

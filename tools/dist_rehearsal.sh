@@ -10,9 +10,9 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$R"
 PAXISIM_DIST_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 4 --warmup 1 --clusters 262144 \
+  --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 4 --warmup 1 --clusters 262144 \
   > "$OUT/bench2.json" 2> "$OUT/bench2.err" || { echo "2-rank bench failed rc=$?"; tail -20 "$OUT/bench2.err"; exit 1; }
 cat "$OUT/bench2.json"
-timeout -k 10 300 python bench.py --steps 4 --warmup 1 --clusters 524288 --no-cpu-baseline > "$OUT/bench1.json" 2> "$OUT/bench1.err" \
+timeout -k 10 300 python bench.py --steps 4 --warmup 1 --clusters 524288 --full --no-cpu-baseline > "$OUT/bench1.json" 2> "$OUT/bench1.err" \
   || { echo "1-rank bench failed rc=$?"; tail -20 "$OUT/bench1.err"; exit 1; }
 cat "$OUT/bench1.json"
