@@ -166,7 +166,7 @@ __global__ void gather_kernel(Params P, uint64_t lo, uint64_t n, paxisim_replica
   s.p1_acks = P.meta[j] >> 16;
   s.flags = P.flags[j];
   s.digest = P.digest[j];
-  s.npending = P.npend[j];
+  s.npending = P.npend[j] & NPEND_MASK;
   for (int k = 0; k < PAXISIM_NMSG; k++) s.delivered[k] = P.stats[krc(P, ST_DELIV0 + k, r, c)];
   s.client_requests = P.stats[krc(P, ST_CLIENT, r, c)];
   s.sent = P.stats[krc(P, ST_SENT, r, c)];
@@ -293,7 +293,7 @@ __global__ void gather_inst_kernel(Params P, uint64_t lo, uint64_t n, paxisim_in
     s.active = P.meta[j] & 1u;
     s.exists = 1;
     s.p1_acks = P.meta[j] >> 16;
-    s.npending = P.npend[j];
+    s.npending = P.npend[j] & NPEND_MASK;
     s.digest = P.digest[j];
     s.policy_last = POL_NONE;
   }
@@ -443,10 +443,15 @@ __global__ void read_log_kernel(Params P, uint64_t cl, uint32_t r, uint32_t key,
     execute = (int32_t)P.execute[rc(P, r, c)];
     const uint8_t* img = P.image + (size_t)blk * P.img.bytes;
     const uint32_t li = ((r * P.W + w) << 6) | lane;
-    eb = reinterpret_cast<const uint32_t*>(img + P.img.off_a)[li];
-    ec = reinterpret_cast<const uint32_t*>(img + P.img.off_b)[li];
-    ea = reinterpret_cast<const uint32_t*>(img + P.img.off_c)[li];
-    ex = P.reqx[(size_t)blk * (P.N * P.W * LANES) + li];
+    if (P.packed) {
+      const uint4 e = P.plog[(size_t)blk * (P.N * P.W * LANES) + li];
+      eb = e.x; ec = e.y; ea = e.z; ex = e.w;
+    } else {
+      eb = reinterpret_cast<const uint32_t*>(img + P.img.off_a)[li];
+      ec = reinterpret_cast<const uint32_t*>(img + P.img.off_b)[li];
+      ea = reinterpret_cast<const uint32_t*>(img + P.img.off_c)[li];
+      ex = P.reqx[(size_t)blk * (P.N * P.W * LANES) + li];
+    }
   }
   if (s >= execute && s < execute + (int32_t)P.W) {
     o.flags = PAXISIM_LOG_HELD;
@@ -515,7 +520,7 @@ __device__ void swap_slots(const Params& P, uint64_t p, uint64_t q, uint32_t j) 
   // live extents, read before any row moves (uniform across the wave)
   for (uint32_t r = 0; r < N; r++) {
     const size_t ip = (size_t)r * C + p, iq = (size_t)r * C + q;
-    const uint32_t np0 = P.npend[ip], np1 = P.npend[iq];
+    const uint32_t np0 = P.npend[ip] & NPEND_MASK, np1 = P.npend[iq] & NPEND_MASK;
     const uint32_t nf0 = P.nfwd[ip], nf1 = P.nfwd[iq];
     const bool gh = ((P.flags[ip] | P.flags[iq]) & PAXISIM_F_GHOST) != 0u;
     const uint32_t np = np0 > np1 ? np0 : np1, nf = nf0 > nf1 ? nf0 : nf1;
@@ -532,7 +537,7 @@ __device__ void swap_slots(const Params& P, uint64_t p, uint64_t q, uint32_t j) 
     if (a) { a[p] = vq; a[q] = vp; }
     if (g) { g[p] = gq; g[q] = gp; }
   }
-  swap_rows(P.ballot, 7 * N, C, p, q, j);        // ballot slot execute meta flags npend nfwd
+  swap_rows(P.ballot, 7 * N, C, p, q, j);        // ballot slot execute meta flags npend (+ committed bits) nfwd
   swap_rows(P.digest, N, C, p, q, j);
   swap_rows(P.kc, 1, C, p, q, j);
   swap_rows(P.link_drop, 2 * N * N, C, p, q, j);   // link_drop then link_slow
@@ -545,8 +550,10 @@ __device__ void swap_slots(const Params& P, uint64_t p, uint64_t q, uint32_t j) 
   swap_rows(P.frz, 1, C, p, q, j);
   swap_rows(P.qf, 1, C, p, q, j);
   if (P.phase_sort) swap_rows(P.phase, 1, C, p, q, j);
-  swap_lanes(P.reqx, (size_t)N * P.W * LANES, (size_t)N * P.W, p, q, j);
-  // LDS image: u32 rows (log window a/b/c, worker tables, poison), then u8 mailbox counts
+  // log windows: the packed entries (rows of 64 uint4), or the request side table beside the image's planes
+  if (P.packed) swap_lanes(P.plog, (size_t)N * P.W * LANES, (size_t)N * P.W, p, q, j);
+  else swap_lanes(P.reqx, (size_t)N * P.W * LANES, (size_t)N * P.W, p, q, j);
+  // LDS image: u32 rows (log window a/b/c where it has them, worker tables, poison), then u8 mailbox counts
   swap_lanes(reinterpret_cast<uint32_t*>(P.image), P.img.bytes / 4u, P.img.off_cnt / (LANES * 4u), p, q, j);
   {
     uint8_t* cp = P.image + (p / LANES) * (size_t)P.img.bytes + P.img.off_cnt + (p % LANES);
@@ -769,7 +776,7 @@ __global__ void replay_kernel(Params P, uint64_t s0, uint64_t s1, uint32_t tnow)
 // C-ABI
 // ---------------------------------------------------------------------------
 static Image proto_image(uint32_t protocol, uint32_t N, uint32_t W, uint32_t K, uint32_t WK, uint32_t D,
-                         uint32_t wlds) {
+                         uint32_t wlds, bool packed) {
   if (protocol == PAXISIM_ABD) {
     const uint32_t kv = N * K * LANES * 4u;
     return image_layout(kv, kv, N * abd_ow(WK) * ABD_OPF * LANES * 4u, N, WK, D);
@@ -777,7 +784,9 @@ static Image proto_image(uint32_t protocol, uint32_t N, uint32_t W, uint32_t K, 
   if (protocol == PAXISIM_WPAXOS)   // instance scalars in the image (wlds), or all in HBM
     return image_layout(wlds ? K * N * WP_WORDS * LANES * 4u : 0u, 0, 0, N, WK, D);
   if (protocol == PAXISIM_EPAXOS) return image_layout(0, 0, 0, N, WK, D);   // state in HBM
-  const uint32_t logb = N * W * LANES * 4u;
+  // Multi-Paxos: the window's three planes, or none - the packed serial units keep their entries
+  // outside the image (Params::plog)
+  const uint32_t logb = packed ? 0u : N * W * LANES * 4u;
   return image_layout(logb, logb, logb, N, WK, D);
 }
 
@@ -867,14 +876,18 @@ static int check_config(const paxisim_config* cfg, const paxisim_workload* wl, c
     if (wl->target[w] >= N) return fail(PAXISIM_EINVAL, "target[%u]", w);
   if (fp->slow_ppm && (fp->slow_min > fp->slow_max || fp->slow_max > cfg->max_delay))
     return fail(PAXISIM_EINVAL, "slow delay range exceeds max_delay");
-  const Image img = proto_image(cfg->protocol, N, cfg->window, cfg->keys, wl->outstanding, cfg->max_delay + 2u, 0);
+  const bool serial = serial_for(cfg->protocol);
+  const Image img = proto_image(cfg->protocol, N, cfg->window, cfg->keys, wl->outstanding, cfg->max_delay + 2u, 0,
+                                serial && cfg->protocol == PAXISIM_PAXOS && paxos_packed(N));
   // the serial kernel keeps only the image's tail (client tables on) in LDS;
   // either kernel adds the agreement-ring arrival counts after the image
   const bool ring = cfg->protocol != PAXISIM_ABD && cfg->protocol != PAXISIM_EPAXOS;
   const uint32_t agn = ring ? (2u * N * LANES + 15u) & ~15u : 0u;
-  if ((serial_for(cfg->protocol) ? img.bytes - img.off_wcur : img.bytes) + agn > LDS_MAX)
-    return fail(PAXISIM_EUNSUPP, "workgroup image %u B exceeds LDS (%u B): reduce window/max_delay/replicas",
-                img.bytes, LDS_MAX);
+  const uint32_t need = (serial ? img.bytes - img.off_wcur : img.bytes) + agn;
+  if (need > LDS_MAX)
+    return fail(PAXISIM_EUNSUPP, "%s %u B exceeds LDS (%u B): reduce %smax_delay/replicas",
+                serial ? "serial LDS (image tail and arrival counts)" : "workgroup image and arrival counts", need,
+                LDS_MAX, serial ? "" : "window/");
   *N_out = N;
   return 0;
 }
@@ -1066,7 +1079,7 @@ extern "C" int paxisim_create(const paxisim_config* cfg, const paxisim_workload*
     const uint32_t agn = P.AR ? (2u * N * LANES + 15u) & ~15u : 0u;
     const bool ser = serial_for(P.protocol);
     P.wlds = (ev ? atoi(ev) != 0 : !ser) &&
-             (ser || proto_image(P.protocol, N, P.W, P.keys, P.WK, P.D, 1).bytes + agn <= LDS_MAX);
+             (ser || proto_image(P.protocol, N, P.W, P.keys, P.WK, P.D, 1, false).bytes + agn <= LDS_MAX);
     // Each instance's 32-B scalars and its window in one block of whole lines: a
     // layout only, the kernels address both through wst_str / wlog_str.  On by default at W = 8, where
     // six of the eight entries share the line the bind loads (mirrored A/B r6g2, config 5: +4.2% over
@@ -1074,7 +1087,10 @@ extern "C" int paxisim_create(const paxisim_config* cfg, const paxisim_workload*
     const char* cv = getenv("PAXISIM_WCOLOC");
     P.wcoloc = !P.wlds && (cv ? atoi(cv) != 0 : P.W == 8u);
   }
-  P.img = proto_image(P.protocol, N, P.W, P.keys, P.WK, P.D, P.wlds);
+  // Multi-Paxos: the window layout goes with the kernel - 16-B entries in plog for the serial units
+  // that take them (paxos_packed), else the image's planes (paxos_kernel.h)
+  P.packed = P.protocol == PAXISIM_PAXOS && serial_for(P.protocol) && paxos_packed(N);
+  P.img = proto_image(P.protocol, N, P.W, P.keys, P.WK, P.D, P.wlds, P.packed != 0);
   {
     // Cluster groups per workgroup (sim_core.h): as many 64-cluster tiles as
     // the step kernel's registers leave wave slots for on every SIMD
@@ -1151,7 +1167,8 @@ extern "C" int paxisim_create(const paxisim_config* cfg, const paxisim_workload*
     uint64_t* ckd = carve<uint64_t>(p, NIC * CKR);
     uint4* gst = carve<uint4>(p, NIC * GMAX);
     uint32_t* st = carve<uint32_t>(p, NC * NSTAT);
-    uint32_t* reqx = carve<uint32_t>(p, wp ? 0 : NC * P.W);
+    uint32_t* reqx = carve<uint32_t>(p, wp || P.packed ? 0 : NC * P.W);
+    uint4* plog = carve<uint4>(p, P.packed ? NC * P.W : 0);
     // WPaxos instances: the scalars table and the windows apart, or (wcoloc) one block per instance
     // holding both - 32 B of scalars, then the window - padded to whole 128-B lines, so the entries
     // at the window's head share the line the bind loads
@@ -1188,7 +1205,7 @@ extern "C" int paxisim_create(const paxisim_config* cfg, const paxisim_workload*
       P.flags = s7 + 4 * NC; P.npend = s7 + 5 * NC; P.nfwd = s7 + 6 * NC;
       P.digest = dg; P.kc = kc; P.pend = pend; P.fwd = fwd;
       P.link_drop = links; P.link_slow = links + NC * N;
-      P.ck_e = cke; P.ck_d = ckd; P.stats = st; P.reqx = reqx; P.hist = hist; P.image = image; P.rec = rec;
+      P.ck_e = cke; P.ck_d = ckd; P.stats = st; P.reqx = reqx; P.plog = plog; P.hist = hist; P.image = image; P.rec = rec;
       P.wst = wst; P.wdig = wdig; P.wlog = wlog; P.wpend = wpend; P.gst = gst; P.wpx = wpx;
       P.wst_str = coloc ? (uint32_t)(wblk_b / 16u) : 2u;
       P.wlog_str = coloc ? (uint32_t)(wblk_b / 4u) : P.W * 4u;

@@ -21,6 +21,15 @@ namespace pxs {
 
 constexpr uint32_t PMAX = 32;   // pending requests per replica (p.requests)
 constexpr uint32_t FMAX = 32;   // forwards table per replica (node.forwards)
+// Params::npend holds the count in its low half; the high half carries a packed Multi-Paxos
+// window's committed bits (paxos_kernel.h cm_note), so every reader of the row masks it
+constexpr uint32_t NPEND_MASK = 0xFFFFu;
+// Which serial Multi-Paxos units keep their windows as packed 16-B entries (paxos_kernel.h): all but
+// the 9-replica one.  Config 2's lanes sit at scattered slots, where one 16-B piece per lane replaces
+// three scattered words (+7.7%); config 4's clusters run in lockstep, its plane rows are read whole,
+// and an entry row moves four times the bytes of the one plane a P3 needs (-9%).
+// n: the unit's replica count (0: the any-N unit), or the simulation's N - the two agree.
+__host__ __device__ constexpr bool paxos_packed(uint32_t n) { return n != 9u; }
 constexpr uint32_t CKI = 16;    // checkpoint interval (executed slots)
 constexpr uint32_t CKR = 8;     // checkpoints kept per replica
 constexpr uint32_t GMAX = 8;    // live entries below execute kept per instance
@@ -31,11 +40,11 @@ constexpr uint32_t LANES = 64;
 constexpr uint32_t LDS_MAX = 160u * 1024u;
 constexpr uint32_t T_MAX = 1u << 28;   // slow_until is packed in 28 bits
 
-// log entry, LDS form: {ballot, cmd | flags, ack mask}
+// log entry: {ballot, cmd | flags, ack mask} (and the request, in the packed form)
 constexpr uint32_t CMD_MASK = 0x07FFFFFFu;
 constexpr uint32_t EF_EXISTS = 1u << 27, EF_COMMIT = 1u << 28, EF_QUORUM = 1u << 29;
 constexpr uint32_t EF_REQSELF = 1u << 30;   // request == (cmd, client): kept implicit
-constexpr uint32_t EF_REQEXT = 1u << 31;    // request in the HBM side table
+constexpr uint32_t EF_REQEXT = 1u << 31;    // request in the entry's fourth word (packed) or the HBM side table (planes)
 
 enum { PUR_ORDER = 1, PUR_LINK = 2, PUR_SLOWD = 3, PUR_FLAKY = 4 };
 
@@ -50,7 +59,9 @@ enum {
 
 // Byte layout of a workgroup's LDS image (identical in HBM, one per block).
 // Regions a/b/c belong to the protocol:
-//   Paxos: log window ballot / cmd|flags / ack mask, each [r][W][lane] u32
+//   Paxos: log window ballot / cmd|flags / ack mask, each [r][W][lane] u32 (sim_steps and the
+//          9-replica serial unit; the other serial units keep 16-B entries in Params::plog and
+//          these regions are empty: paxos_packed)
 //   ABD:   KV value / KV version [r][K][lane] u32, op table [r][OW][6][lane] u32
 struct Image {
   uint32_t off_a, off_b, off_c, off_wcur, off_wiss, off_poison, off_cnt, bytes;
@@ -157,7 +168,9 @@ struct Params {
   uint32_t AR;           // checkpoints kept per (cluster, instance); 0 = no agreement ring
   uint4* agq;            // [2][AGMAX][N][C] a step's ring arrivals {entry lo, entry hi, key, 0}, by step parity
   uint32_t off_agn;      // LDS byte offset of the arrival counts [2][N][lane] u8 (per tile, outside the image)
-  uint32_t* reqx;        // [blk][N][W][64] request side table (Paxos)
+  uint32_t* reqx;        // [blk][N][W][64] request side table (Paxos, plane layout)
+  uint4* plog;           // [blk][N][W][64] {ballot, cmd|flags, acks, request}: the Multi-Paxos windows of the packed serial units
+  uint32_t packed;       // 1: Multi-Paxos windows in plog (chosen at create with the kernel: paxos_packed), 0: image regions a/b/c + reqx
   uint4* hist;           // [N][C][H] completed ABD ops {key|write<<31, value, start, end}
   uint8_t* image;        // [blk][img.bytes]
   unsigned long long* dbg;  // diagnostic build only (PXS_STAMPS): per-wave phase totals

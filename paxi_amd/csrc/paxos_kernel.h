@@ -6,17 +6,20 @@
 //
 // Paxos state during a launch:
 //   registers: ballot, slot, execute, active, phase-1 acks, pending/forward counts, digest
-//   log window {ballot, cmd|flags, acks} as [r][W][lane] u32 (regions a, b, c of
-//              the tile image): in the HBM image for the serial kernels (the
-//              product, sim_serial*), in LDS for the rounds-1-2 sim_steps kernel
-//   HBM:       request side table, pending/forward tables, digest checkpoints
+//   log window serial kernels (the product, sim_serial*) but the 9-replica one:
+//              16-B entries {ballot, cmd|flags, acks, request} as [blk][r][W][lane]
+//              in HBM (P.plog), read through a one-entry register cache; else
+//              three u32 planes [r][W][lane] (regions a, b, c of the tile image)
+//              and the request side table in HBM - the planes in the HBM image
+//              (9-replica serial unit) or in LDS (the rounds-1-2 sim_steps kernel)
+//   HBM:       pending/forward tables, digest checkpoints
 #pragma once
 #include "sim_core.h"
 
 namespace pxs {
 
 // ---------------------------------------------------------------------------
-// log window (HBM image, or LDS in sim_steps): entry of slot s of replica r at [(r*W + (s & (W-1)))*64 + lane]
+// log window: entry of slot s at word x.e0 + (s & (W-1)) * x.es of x.l_a (packed), or of each plane
 // ---------------------------------------------------------------------------
 struct Ent { uint32_t b, c, a; };
 
@@ -27,20 +30,35 @@ struct Ent { uint32_t b, c, a; };
 #define PXS_TALLY_X(x, cls, ptr, st)
 #endif
 
-// Two layouts share these handlers.  Multi-Paxos keeps each replica's window
-// in LDS as three u32 planes (l_a / l_b / l_c, entry stride es = 64 lanes) and
-// the request side table in HBM (reqx).  The per-key instances of WPaxos keep
-// theirs in HBM as one 16-B entry {ballot, cmd|flags, acks, request} per slot
-// (es = 4 words): reads go through a one-entry register cache that the
-// dispatcher fills before the handler runs (its load overlaps the instance
-// bind), and writes go through to HBM.  es is a compile-time constant of each
-// kernel instance (sim_steps sets it before any use), so the branch folds.
+// Two entry layouts share these handlers, and two kinds of instance.
+//
+// Layout.  Packed: one 16-B entry {ballot, cmd|flags, acks, request} per slot
+// in HBM - the serial kernels (paxisim_dev.h paxos_packed).  Reads go through a one-entry register cache
+// (a P2b's ballot, flags and acks arrive in one round trip; a per-key
+// dispatcher fills it before the handler runs, so the load overlaps the bind),
+// writes go through to HBM, and cmask keeps the committed bit of every window
+// slot so that exec() stops without reading the next entry.  A per-key
+// instance's window is the lane's own, entries 4 words apart; Multi-Paxos's is
+// lane-minor, [r][W][lane], entries 4 * 64 words apart, so that a wave - whose
+// lanes run the same replica and mostly neighbouring slots - reads one 1-KB
+// row.  Planes: three u32 planes (l_a / l_b / l_c, entries 64 words apart) and
+// the request side table in HBM (reqx) - Multi-Paxos in sim_steps, with the
+// planes in LDS, and in the 9-replica serial unit, with the planes in HBM.
+//
+// Instance.  Per-key (x.pk): one of a replica's K instances (WPaxos, M2Paxos,
+// KPaxos), which executes commands of its own key only and keeps its ghosts,
+// digest and forwards table accordingly; or the replica's one (Multi-Paxos).
+//
+// x.es and x.pk are compile-time constants of each kernel instance (set once
+// at the kernel's entry), so these branches fold.
 template <int NT>
 __device__ __forceinline__ uint32_t eidx(const Params& P, const Rep<NT>& x, int32_t s) {
   return x.e0 + ((uint32_t)s & (P.W - 1u)) * x.es;
 }
 template <int NT>
-__device__ __forceinline__ bool hbm_log(const Rep<NT>& x) { return x.es == 4u; }
+__device__ __forceinline__ bool packed_log(const Rep<NT>& x) { return x.es != LANES; }
+template <int NT>
+__device__ __forceinline__ bool per_key(const Rep<NT>& x) { return x.pk; }
 template <int NT>
 __device__ __forceinline__ void ecache(Rep<NT>& x, uint32_t i) {
   if (x.ci != i) {
@@ -51,59 +69,53 @@ __device__ __forceinline__ void ecache(Rep<NT>& x, uint32_t i) {
 }
 template <int NT>
 __device__ __forceinline__ uint32_t ea(Rep<NT>& x, uint32_t i) {
-  if (hbm_log(x)) { ecache(x, i); return x.ce.x; }
+  if (packed_log(x)) { ecache(x, i); return x.ce.x; }
   PXS_TALLY_X(x, TC_ENT_LD, x.l_a + i, false);
   return x.l_a[i];
 }
 template <int NT>
 __device__ __forceinline__ uint32_t eb(Rep<NT>& x, uint32_t i) {
-  if (hbm_log(x)) { ecache(x, i); return x.ce.y; }
+  if (packed_log(x)) { ecache(x, i); return x.ce.y; }
   PXS_TALLY_X(x, TC_ENT_LD, x.l_b + i, false);
   return x.l_b[i];
 }
 template <int NT>
 __device__ __forceinline__ uint32_t ec(Rep<NT>& x, uint32_t i) {
-  if (hbm_log(x)) { ecache(x, i); return x.ce.z; }
-  if (wb_on(x) && x.ci == i) return x.ce.z;
+  if (packed_log(x)) { ecache(x, i); return x.ce.z; }
   PXS_TALLY_X(x, TC_ENT_LD, x.l_c + i, false);
   return x.l_c[i];
 }
 template <int NT>
 __device__ __forceinline__ void set_a(Rep<NT>& x, uint32_t i, uint32_t v) {
   PXS_TALLY_X(x, TC_ENT_ST, x.l_a + i, true);
-  if (hbm_log(x)) { x.l_a[i] = v; if (x.ci == i) x.ce.x = v; return; }
   x.l_a[i] = v;
+  if (packed_log(x) && x.ci == i) x.ce.x = v;
 }
-// committed-entry bits of an HBM-resident window: exec() stops at the first
-// clear bit without reading the entry (W <= 16; wider windows read it)
+// committed-entry bits of a packed window: exec() stops at the first clear bit
+// without reading the entry (W <= 16; wider windows read it).  Every write of
+// an entry's flags word comes through here (set_b, eput).
 template <int NT>
 __device__ __forceinline__ void cm_note(Rep<NT>& x, uint32_t i, uint32_t c) {
-  const uint32_t bit = 1u << ((i >> 2) & 31u);
+  const uint32_t bit = 1u << ((per_key(x) ? i >> 2 : (i - x.e0) >> 8) & 31u);
   x.cmask = (c & EF_COMMIT) ? (x.cmask | bit) : (x.cmask & ~bit);
 }
 template <int NT>
 __device__ __forceinline__ void set_b(Rep<NT>& x, uint32_t i, uint32_t v) {
-  PXS_TALLY_X(x, TC_ENT_ST, hbm_log(x) ? x.l_a + i + 1u : x.l_b + i, true);
-  if (hbm_log(x)) { x.l_a[i + 1u] = v; if (x.ci == i) x.ce.y = v; cm_note(x, i, v); return; }
+  PXS_TALLY_X(x, TC_ENT_ST, packed_log(x) ? x.l_a + i + 1u : x.l_b + i, true);
+  if (packed_log(x)) { x.l_a[i + 1u] = v; if (x.ci == i) x.ce.y = v; cm_note(x, i, v); return; }
   x.l_b[i] = v;
 }
 template <int NT>
 __device__ __forceinline__ void set_c(Rep<NT>& x, uint32_t i, uint32_t v) {
-  PXS_TALLY_X(x, TC_ENT_ST, hbm_log(x) ? x.l_a + i + 2u : x.l_c + i, true);
-  if (hbm_log(x)) { x.l_a[i + 2u] = v; if (x.ci == i) x.ce.z = v; return; }
-  if (wb_on(x)) {
-    if (x.ci != i) wb_flush(x);
-    x.ci = i;
-    x.ce.z = v;
-    return;
-  }
+  PXS_TALLY_X(x, TC_ENT_ST, packed_log(x) ? x.l_a + i + 2u : x.l_c + i, true);
+  if (packed_log(x)) { x.l_a[i + 2u] = v; if (x.ci == i) x.ce.z = v; return; }
   x.l_c[i] = v;
 }
 template <int NT>
 __device__ __forceinline__ Ent eget(Rep<NT>& x, uint32_t i) { return Ent{ea(x, i), eb(x, i), ec(x, i)}; }
 template <int NT>
 __device__ __forceinline__ void eput(Rep<NT>& x, uint32_t i, const Ent& e) {
-  if (hbm_log(x)) {                                  // one 12-B store
+  if (packed_log(x)) {                               // one 12-B store
     uint32_t* q = x.l_a + i;
     PXS_TALLY_X(x, TC_ENT_ST, q, true);
     *reinterpret_cast<uint2*>(q) = make_uint2(e.b, e.c);
@@ -112,7 +124,6 @@ __device__ __forceinline__ void eput(Rep<NT>& x, uint32_t i, const Ent& e) {
     cm_note(x, i, e.c);
     return;
   }
-  if (wb_on(x) && x.ci == i) x.ci = ~0u;            // superseded by this write
   PXS_TALLY_X(x, TC_ENT_ST, x.l_a + i, true);
   PXS_TALLY_X(x, TC_ENT_ST, x.l_b + i, true);
   PXS_TALLY_X(x, TC_ENT_ST, x.l_c + i, true);
@@ -120,17 +131,17 @@ __device__ __forceinline__ void eput(Rep<NT>& x, uint32_t i, const Ent& e) {
   x.l_b[i] = e.c;
   x.l_c[i] = e.a;
 }
-// request side table entry for log entry index i
+// the request of log entry index i: the entry's fourth word, or the side table's
 template <int NT>
 __device__ __forceinline__ uint32_t rq_get(Rep<NT>& x, uint32_t i) {
-  if (hbm_log(x)) { ecache(x, i); return x.ce.w; }
+  if (packed_log(x)) { ecache(x, i); return x.ce.w; }
   PXS_TALLY_X(x, TC_OTHER, &x.reqx[i], false);
   return ldg(&x.reqx[i]);
 }
 template <int NT>
 __device__ __forceinline__ void rq_set(Rep<NT>& x, uint32_t i, uint32_t q) {
-  PXS_TALLY_X(x, hbm_log(x) ? TC_ENT_ST : TC_OTHER, hbm_log(x) ? x.l_a + i + 3u : &x.reqx[i], true);
-  if (hbm_log(x)) { x.l_a[i + 3u] = q; if (x.ci == i) x.ce.w = q; return; }
+  PXS_TALLY_X(x, packed_log(x) ? TC_ENT_ST : TC_OTHER, packed_log(x) ? x.l_a + i + 3u : &x.reqx[i], true);
+  if (packed_log(x)) { x.l_a[i + 3u] = q; if (x.ci == i) x.ce.w = q; return; }
   x.reqx[i] = q;
 }
 template <int NT>
@@ -174,7 +185,7 @@ __device__ __forceinline__ void request_reply(const Params& P, Rep<NT>& x, uint3
 // index of cid in the forwards table, or nfwd: four probes per round trip
 template <int NT>
 __device__ __forceinline__ uint32_t fwd_find(const Params& P, const Rep<NT>& x, uint32_t cid) {
-  if (!hbm_log(x)) {                                     // (A/B r2: the LDS-window kernels keep one probe per trip)
+  if (!per_key(x)) {                                     // (A/B r2: the Multi-Paxos kernels keep one probe per trip)
     uint32_t i = 0;
     for (; i < x.nfwd; i++) {
       PXS_TALLY_AT(P, x.blk, TC_FWD, &P.fwd[krc(P, i, x.r, x.c)], false);
@@ -215,14 +226,13 @@ __device__ __forceinline__ void node_forward(const Params& P, Rep<NT>& x, uint32
   post_unicast<NT>(P, x, to, PAXISIM_MSG_REQUEST, 0u, 0u, cid);
 }
 
-// node.recv Reply case (node.go:83-90).  With the table in HBM (the per-key
-// kernels) the probe keeps the four entries it loaded: the request found is
+// node.recv Reply case (node.go:83-90).  In the per-key kernels the probe keeps the four entries it loaded: the request found is
 // one of them, and so is the table's last entry (moved into the freed place)
-// whenever it lies in the same group - one round trip where the LDS-window
+// whenever it lies in the same group - one round trip where the Multi-Paxos
 // kernels' probe-then-reload path takes three.
 template <int NT>
 __device__ __forceinline__ void handle_reply(const Params& P, Rep<NT>& x, uint32_t cid, uint32_t value) {
-  if (hbm_log(x)) {
+  if (per_key(x)) {
     const uint32_t last = x.nfwd - 1u;
     for (uint32_t i0 = 0; i0 < x.nfwd; i0 += 4u) {
       uint32_t f[4];
@@ -287,14 +297,14 @@ __device__ __forceinline__ void raise_win(Rep<NT>& x, uint32_t f) {
 // steps of the execution: a ghost lives that long after it is (re)created,
 // in a per-instance table in HBM {slot, ballot, until | commit << 31} touched
 // only on these paths.  iflags GHOST = the table may hold a live entry.
-// Ghost table addressing.  Per-key instances (HBM log) keep a lane's GMAX
+// Ghost table addressing.  Per-key instances keep a lane's GMAX
 // ghosts of one instance in one 128-B line ([NI][C][GMAX]), so the probes
 // after the first hit in cache; Multi-Paxos keeps [GMAX][NI][C] (A/B r2: the
-// line layout costs its LDS-window kernels registers).  The probes stay
+// line layout costs its kernels registers).  The probes stay
 // serial (ldg): eight in flight at once would cost 32 registers.
 template <int NT>
 __device__ __forceinline__ uint4* gref(const Params& P, const Rep<NT>& x, uint32_t g) {
-  uint4* q = hbm_log(x) ? &P.gst[((size_t)x.inst * P.C + x.c) * GMAX + g] : &P.gst[((size_t)g * P.NI + x.inst) * P.C + x.c];
+  uint4* q = per_key(x) ? &P.gst[((size_t)x.inst * P.C + x.c) * GMAX + g] : &P.gst[((size_t)g * P.NI + x.inst) * P.C + x.c];
   PXS_TALLY_AT(P, x.blk, TC_GHOST, q, false);   // (every use of a ghost reference counted as a line)
   return q;
 }
@@ -455,8 +465,8 @@ __device__ __forceinline__ void handle_request(const Params& P, Rep<NT>& x, uint
 // (the key is computed once per executed command: kv_key)
 template <int NT>
 __device__ __forceinline__ uint32_t kv_key(const Params& P, Rep<NT>& x, uint32_t h, uint32_t cmd) {
-  // a per-key instance (HBM log: WPaxos, M2Paxos, KPaxos) only executes commands of its own key
-  return hbm_log(x) ? x.key : key_fit<NT>(P, x, wl_key_h(P, h, cmd));
+  // a per-key instance (WPaxos, M2Paxos, KPaxos) only executes commands of its own key
+  return per_key(x) ? x.key : key_fit<NT>(P, x, wl_key_h(P, h, cmd));
 }
 template <int NT>
 __device__ __forceinline__ uint32_t kv_get(const Params& P, Rep<NT>& x, uint32_t key) {
@@ -474,36 +484,33 @@ __device__ __forceinline__ void kv_exec(const Params& P, Rep<NT>& x, uint32_t h,
 }
 
 // hi / hc: the entry index and flags the caller has just written, which exec
-// then does not read back.  With the window in HBM (three planes, the serial
-// kernel) each slot's iteration loads the next slot's flags before it issues
-// its own stores (PXS_EXEC_AHEAD), so the loop's exit test does not wait for
-// them (vmcnt retires loads and stores in issue order).
+// then does not read back.  With the planes in HBM (the 9-replica serial unit)
+// each slot's iteration loads the next slot's flags before it issues its own
+// stores, so the loop's exit test does not wait for them (vmcnt retires loads
+// and stores in issue order).
 // A WPaxos bind (wlds) does not load the instance's digest: exec, its only
 // reader, loads it on first use, and the unbind stores it only if exec changed it.
 template <int NT>
 __device__ __forceinline__ void digest_need(const Params& P, Rep<NT>& x) {
-  if (hbm_log(x) && P.wlds && x.dig_st == 0u) {
+  if (per_key(x) && P.wlds && x.dig_st == 0u) {
     PXS_TALLY_AT(P, x.blk, TC_CKPT, &P.wdig[wp_si(P, x.blk, x.key, x.r, x.lane)], false);
     x.digest = P.wdig[wp_si(P, x.blk, x.key, x.r, x.lane)];
     x.dig_st = 1u;
   }
 }
-#ifndef PXS_EXEC_AHEAD
-#define PXS_EXEC_AHEAD 1
-#endif
 template <int NT>
 __device__ __forceinline__ void paxos_exec(const Params& P, Rep<NT>& x, uint32_t hi = ~0u,
                                            uint32_t hc = 0u) {     // paxos.go:345-369
-  uint32_t ni = ~0u, nc = 0u;                                      // the next slot's entry, loaded ahead
+  uint32_t ni = ~0u, nc = 0u;                                      // the next slot's flags, loaded ahead
   for (;;) {
-    if (hbm_log(x)) {                                              // skip the HBM read of an uncommitted entry
+    if (packed_log(x)) {                                           // skip the HBM read of an uncommitted entry
       if (P.W <= 16u ? !((x.cmask >> ((uint32_t)x.execute & (P.W - 1u))) & 1u) : x.execute > x.slot) break;
     }
     const uint32_t i = eidx<NT>(P, x, x.execute);
     const uint32_t c = i == hi ? hc : (i == ni ? nc : eb(x, i));
     hi = ~0u;
     if ((c & (EF_EXISTS | EF_COMMIT)) != (EF_EXISTS | EF_COMMIT)) break;
-    if (PXS_EXEC_AHEAD && x.hw && !hbm_log(x)) {
+    if (x.hw && !packed_log(x)) {
       ni = eidx<NT>(P, x, x.execute + 1);
       nc = x.l_b[ni];
     }
@@ -788,17 +795,24 @@ struct PaxosProto {
     const uint32_t meta = P.meta[i];
     x.active = meta & 1u;
     x.p1mask = meta >> 16;
-    x.npend = P.npend[i];
+    // the committed-window bits of a packed window ride in the spare half of the npend row
+    const uint32_t np = P.npend[i];
+    x.npend = np & NPEND_MASK;
+    x.cmask = np >> 16;
     x.nfwd = P.nfwd[i];
     x.digest = P.digest[i];
-    // the replica's one instance: LDS log window [r][W][lane], SoA pending table
+    // the replica's one instance: log window [r][W][lane], SoA pending table
     x.iflags = x.flags & (PAXISIM_F_WOVF | PAXISIM_F_GHOST);
     x.inst = x.r;
     x.key = 0;
     x.ktag = 0;
     x.e0 = ((x.r * P.W) << 6) | x.lane;
-    x.es = LANES;
-    x.reqx = P.reqx + (size_t)x.blk * (P.N * P.W * LANES);
+    if (packed_log(x)) {               // 16-B entries of the tile's array, a row of 64 per (replica, slot)
+      x.e0 *= 4u;
+      x.l_a = reinterpret_cast<uint32_t*>(P.plog + (size_t)x.blk * (P.N * P.W * LANES));
+    } else {
+      x.reqx = P.reqx + (size_t)x.blk * (P.N * P.W * LANES);
+    }
     x.pend = P.pend + i;
     x.pstride = P.NI * (uint32_t)P.C;
   }
@@ -818,7 +832,7 @@ struct PaxosProto {
     P.slot[i] = (uint32_t)x.slot;
     P.execute[i] = (uint32_t)x.execute;
     P.meta[i] = (x.active & 1u) | (x.p1mask << 16);
-    P.npend[i] = x.npend;
+    P.npend[i] = packed_log(x) ? x.npend | (x.cmask << 16) : x.npend;
     P.nfwd[i] = x.nfwd;
     P.digest[i] = x.digest;
   }

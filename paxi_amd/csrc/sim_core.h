@@ -30,12 +30,13 @@ struct Rep {
   uint32_t ktag;                        // WPaxos: key << 16, tagged onto P1a..P3 records
   uint32_t key, exists, pol;            // WPaxos: key, r.paxi[key] != nil, policy last | hits << 8
   uint32_t iflags;                      // WOVF / GHOST of the bound instance
-  uint32_t e0, es;                      // log entry i of slot s: e0 + (s & (W-1)) * es
-  uint4 ce;                             // HBM-resident window (es = 4): entry at word ci, cached (paxos_kernel.h)
+  uint32_t e0, es;                      // log entry i of slot s: e0 + (s & (W-1)) * es (words; es a kernel constant)
+  uint4 ce;                             // packed window (es != LANES): entry at word ci, cached (paxos_kernel.h)
   uint32_t ci;
-  uint32_t cmask;                       // HBM-resident window: committed entries, one bit per window slot (W <= 16)
+  uint32_t cmask;                       // packed window: committed entries, one bit per window slot (W <= 16)
+  bool pk;                              // the bound instance is one of a replica's per-key instances (a kernel constant)
   bool hw;                              // the log window is in HBM (a kernel constant: sim_serial)
-  uint32_t* reqx;                       // request side table, indexed like the log
+  uint32_t* reqx;                       // request side table of the plane layout, indexed like the log
   uint32_t* pend;                       // pending request k at pend[k * pstride]
   uint32_t pstride;
   uint32_t dvp[PAXISIM_NMSG / 2];       // delivered by type, two 16-bit counts per word (constant-indexed)
@@ -252,7 +253,7 @@ template <int NT>
 __device__ __forceinline__ void intent_flush(const Params& P, Rep<NT>& x) {
   if (!x.im) return;
   constexpr uint32_t NU = NT ? (uint32_t)NT : (uint32_t)PAXISIM_MAX_N;
-  if (NT == 9 && PXS_FLUSH1_9 && x.es == 4u) {   // (the HBM-log kernel: A/B r2 +, the LDS-window one -)
+  if (NT == 9 && PXS_FLUSH1_9 && x.pk) {   // (the per-key kernel: A/B r2 +, the Multi-Paxos LDS-window one -)
 #pragma unroll
     for (uint32_t d = 0; d < NU; d++) {
       if (!((x.im >> d) & 1u)) continue;
@@ -1058,8 +1059,9 @@ __global__ void __launch_bounds__(max_threads<NT>(), min_waves<NT>()) sim_steps(
   if (P.AR)   // this launch's arrival counts (drained every step, so they start empty)
     for (uint32_t k = (wave - grp * N) * LANES + x.lane; k < 2u * N * LANES; k += N * LANES) x.l_agn[k] = 0;
   const bool live = x.c < bound && x.r < N;
-  // the log layout is a constant of the instance (paxos_kernel.h: hbm_log)
+  // the log layout is a constant of the instance (paxos_kernel.h: packed_log, per_key)
   x.es = Proto::kind == PAXISIM_WPAXOS ? 4u : LANES;
+  x.pk = Proto::kind == PAXISIM_WPAXOS;
   x.hw = Proto::kind == PAXISIM_WPAXOS;
   x.ci = ~0u;
   if (live) {
@@ -1167,24 +1169,6 @@ __global__ void __launch_bounds__(max_threads<NT>(), min_waves<NT>()) sim_steps(
 // the HBM image), so many more tiles are resident per CU.  The replica's
 // registers are loaded from and stored to HBM around each replica-step.
 // ---------------------------------------------------------------------------
-// PXS_WB_ACK: with the three planes in HBM (the serial Multi-Paxos kernel) the
-// ack word a P2b writes is held back in (ci, ce.z) and stored after the next
-// trip's entry loads have issued, so their waits do not include it (vmcnt
-// retires loads and stores in issue order).  Every reader of plane c goes
-// through ec(), a direct write of index ci drops the pending one, and each
-// replica-step ends with wb_flush (paxos_kernel.h set_c / eput).
-#ifndef PXS_WB_ACK
-#define PXS_WB_ACK 0
-#endif
-template <int NT>
-__device__ __forceinline__ bool wb_on(const Rep<NT>& x) { return PXS_WB_ACK && x.hw && x.es != 4u; }
-template <int NT>
-__device__ __forceinline__ void wb_flush(Rep<NT>& x) {
-  if (wb_on(x) && x.ci != ~0u) {
-    x.l_c[x.ci] = x.ce.z;
-    x.ci = ~0u;
-  }
-}
 // Replica order per lane (PXS_BUSY_FIRST).  The replica-steps of one step are
 // independent - every send lands in a later step's bucket - so each lane may
 // run its cluster's replicas in any order.  A wave's replica-step lasts as long
@@ -1335,7 +1319,6 @@ __device__ __forceinline__ void step_async(const Params& P, Rep<NT>& x, uint64_t
       for (uint32_t s = 0; s < NSMAX; s++)
         if (s < NS) x.l_cnt[((box0 + s) << 6) | x.lane] = 0;
       if (x.stop) atomicMin(&x.l_poison[x.lane], x.t);
-      wb_flush<NT>(x);
       P.flags[ri0] = x.flags;
       if (P.kv) P.kv_ver[ri0] = x.kvver;
       Proto::template store<NT>(P, x);
@@ -1541,8 +1524,12 @@ __device__ __forceinline__ void serial_tile(const Params& P, uint32_t blk, uint3
   if (P.phase_sort)
     for (uint32_t k = 0; k < P.phase_period; k++) reinterpret_cast<uint32_t*>(x.l_cnt + P.ph_rel)[(k << 6) | x.lane] = 0;
   const bool live = x.c < bound;
-  x.es = Proto::kind == PAXISIM_WPAXOS ? 4u : LANES;
-  x.hw = true;   // every window is in the HBM image here
+  // every window is in HBM here.  16-B entries: a per-key instance's lane by lane (wpaxos_kernel.h),
+  // Multi-Paxos's lane-minor, one 1-KB row per (replica, slot) (paxos_kernel.h PaxosProto::load); or,
+  // in the 9-replica Multi-Paxos unit, the image's three planes (paxisim_dev.h paxos_packed)
+  x.es = Proto::kind == PAXISIM_WPAXOS ? 4u : paxos_packed((uint32_t)NT) ? 4u * LANES : LANES;
+  x.pk = Proto::kind == PAXISIM_WPAXOS;
+  x.hw = true;
   x.kc = live ? P.kc[x.c] : 0u;
   uint32_t b0 = t0 % P.D;
   const bool skip_idle = skip_idle_on<Proto>() && !P.drop_ppm && !P.slow_ppm;
@@ -1600,7 +1587,6 @@ __device__ __forceinline__ void serial_tile(const Params& P, uint32_t blk, uint3
 #else
         replica_step<NT, Proto, false>(P, x);
 #endif
-        wb_flush<NT>(x);
         if (!row_dirty_on<Proto>() || x.flags != flags0) {
           PXS_TALLY_AT(P, x.blk, TC_ROW_ST, &P.flags[i], true);
           P.flags[i] = x.flags;
