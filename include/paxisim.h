@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define PAXISIM_ABI_VERSION 13
+#define PAXISIM_ABI_VERSION 14
 
 #define PAXISIM_MAX_N        16  /* replicas per cluster (ack masks are u16) */
 #define PAXISIM_MAX_ZONES    16
@@ -475,6 +475,44 @@ int  paxisim_quorum(const paxisim_config* cfg, uint32_t kind, uint32_t ack_mask,
 
 /* Bytes of device memory held by the handle. */
 int  paxisim_device_bytes(paxisim* h, uint64_t* bytes);
+
+/* ---- Client request latency (stat.go:12-66, benchmark.go:186; DESIGN.md
+ * §3.12).  The latency of a command is the step in which its reply is accepted
+ * by its closed-loop worker minus the step in which the worker issued it (a
+ * worker's first request is issued at start_step[w]); it is exact in virtual
+ * steps and the same on every backend.  The device keeps, per worker, an exact
+ * histogram of `bins` one-step bins, the count of samples >= bins, and the
+ * exact sum, min and max of all samples. */
+#define PAXISIM_LAT_MAX_BINS 4096
+#define PAXISIM_ALL_WORKERS  0xFFFFFFFFu
+typedef struct paxisim_latency {      /* one worker, or all workers summed */
+  uint64_t count, sum, overflow;      /* samples; sum of steps; samples >= bins */
+  uint32_t min, max;                  /* exact; UINT32_MAX / 0 when count == 0 */
+  uint32_t bins, pad;
+} paxisim_latency;
+typedef struct paxisim_latency_stat { /* stat.go:12-22, in ms = steps * step_ms */
+  uint64_t size;
+  double mean, min, max, median, p95, p99, p999;
+  uint32_t exact, pad;                /* 0: a percentile fell in the overflow bin */
+} paxisim_latency_stat;
+/* Start recording: bins is a power of two in [16, PAXISIM_LAT_MAX_BINS].  Only
+ * before the first step, and once (EINVAL otherwise).  A handle that never
+ * calls it records nothing and computes exactly what it did before. */
+int  paxisim_latency_enable(paxisim* h, uint32_t bins);
+/* Zero the accumulators and keep the issue stamps (excludes a warm-up): a
+ * request issued before the reset and answered after it counts in full. */
+int  paxisim_latency_reset(paxisim* h);
+/* Worker `worker`'s samples, or (PAXISIM_ALL_WORKERS) every worker's summed;
+ * hist receives out->bins counts or is NULL.  EINVAL when latency is not
+ * enabled or the worker does not exist. */
+int  paxisim_latency_get(paxisim* h, uint32_t worker, paxisim_latency* out, uint64_t* hist);
+/* Stat.Statistic (stat.go:44-66) of a histogram: element int(p * size) of the
+ * sorted samples for p = 0.5, 0.95, 0.99, 0.999, read off the cumulative
+ * counts; a percentile inside the overflow bin reports max and clears `exact`.
+ * A host function, no device needed.  EINVAL when count == 0, ERANGE when
+ * bins exceeds PAXISIM_LAT_MAX_BINS. */
+int  paxisim_latency_stat_of(const paxisim_latency* l, const uint64_t* hist, double step_ms,
+                             paxisim_latency_stat* out);
 
 /* ---- Multi-GPU: clusters shard by range over handles
  * (paxisim_config.cluster_base = rank * clusters), the simulation itself has

@@ -6,7 +6,7 @@ structs, so the two speak exactly the same ABI.
 """
 import ctypes as C
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 MAX_N = 16
 MAX_ZONES = 16
 MAX_WORKERS = 32
@@ -17,6 +17,8 @@ MAX_MBOX = 64
 MAX_DELAY = 14
 CLIENT_SRC = 31
 ALL_DST = 0xFF
+LAT_MAX_BINS = 4096          # paxisim_latency_enable: bins is a power of two in [16, LAT_MAX_BINS]
+ALL_WORKERS = 0xFFFFFFFF     # paxisim_latency_get: every worker summed
 
 # error codes
 OK, EINVAL, ENOMEM, EDEVICE, EUNSUPP, ERANGE = 0, -1, -2, -3, -4, -5
@@ -186,6 +188,22 @@ class WorkerState(C.Structure):
 
     def as_tuple(self):
         return (self.cid, self.issued, self.reply_value)
+
+
+class Latency(C.Structure):
+    """paxisim_latency: the samples of one worker, or of all workers summed (latencies in steps)."""
+    _fields_ = [("count", C.c_uint64), ("sum", C.c_uint64), ("overflow", C.c_uint64),
+                ("min", C.c_uint32), ("max", C.c_uint32), ("bins", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class LatencyStat(C.Structure):
+    """paxisim_latency_stat: Stat of stat.go:12-22, in ms = steps * step_ms."""
+    _fields_ = [("size", C.c_uint64), ("mean", C.c_double), ("min", C.c_double), ("max", C.c_double),
+                ("median", C.c_double), ("p95", C.c_double), ("p99", C.c_double), ("p999", C.c_double),
+                ("exact", C.c_uint32), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("size", "mean", "min", "max", "median", "p95", "p99", "p999", "exact")}
 
 
 class Stats(C.Structure):

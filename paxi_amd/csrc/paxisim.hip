@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <vector>
 
+#define PXS_LAT_REDUCE   // this unit defines and launches lat_reduce (lat_kernel.h)
 #include "epaxos_kernel.h"
 #include "lin_kernel.h"
 #include "paxisim_dev.h"
@@ -72,6 +73,9 @@ struct paxisim {
   uint32_t late_until = 0;         // no compaction before every late worker has started
   uint32_t bound_host = 0;         // last bound read back (diagnostics)
   uint64_t lin_big = 0, lin_nmax = 0;   // last linearizability scan: partitions above LIN_SMAX, largest
+  // client request latency (lat_kernel.h): P.lat_stamp, P.lat_acc and the folded readout [WK][bins + LAT_EXTRA]
+  unsigned long long* d_lat_out = nullptr;
+  size_t lat_bytes = 0;
 };
 
 static inline size_t rc_host(const Params& P, uint32_t r, uint64_t c) { return (size_t)r * P.C + c; }
@@ -547,6 +551,7 @@ __device__ void swap_slots(const Params& P, uint64_t p, uint64_t q, uint32_t j) 
   swap_rows(P.kv_val, P.kv ? (size_t)P.keys * N : 0, C, p, q, j);
   swap_rows(P.kv_ver, P.kv ? N : 0, C, p, q, j);
   swap_rows(P.wrep, P.WK, C, p, q, j);
+  if (P.lat_bins) swap_rows(P.lat_stamp, P.WK, C, p, q, j);   // the issue stamps belong to the cluster
   swap_rows(P.frz, 1, C, p, q, j);
   swap_rows(P.qf, 1, C, p, q, j);
   if (P.phase_sort) swap_rows(P.phase, 1, C, p, q, j);
@@ -928,6 +933,9 @@ extern "C" int paxisim_destroy(paxisim* h) {
   if (h->d_cmp) (void)hipFree(h->d_cmp);
   if (h->d_pairs) (void)hipFree(h->d_pairs);
   if (h->d_pipe) (void)hipFree(h->d_pipe);
+  if (h->P.lat_stamp) (void)hipFree(h->P.lat_stamp);
+  if (h->P.lat_acc) (void)hipFree(h->P.lat_acc);
+  if (h->d_lat_out) (void)hipFree(h->d_lat_out);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return 0;
@@ -944,6 +952,32 @@ static StepOps step_ops_for(uint32_t protocol, uint32_t N, bool wlds, bool seria
   if (protocol == PAXISIM_ABD) return abd_step_ops(N);
   if (protocol == PAXISIM_EPAXOS) return epaxos_step_ops(N);
   return paxos_step_ops(N);
+}
+
+// The same units built with PXS_LAT = 1 (paxisim_dev.h): the step kernels that record client
+// request latency.  Their StepOps and Params are the declarations of step_ops.h and
+// paxisim_dev.h under another namespace, so the layouts are equal.
+namespace pxs_lat {
+pxs::StepOps paxos_serial_step_ops(uint32_t N);
+pxs::StepOps abd_serial_step_ops(uint32_t N);
+pxs::StepOps wpaxos_serial_step_ops(uint32_t N, bool lds);
+pxs::StepOps epaxos_serial_step_ops(uint32_t N);
+pxs::StepOps paxos_step_ops(uint32_t N);
+pxs::StepOps abd_step_ops(uint32_t N);
+pxs::StepOps wpaxos_step_ops(uint32_t N, bool lds);
+pxs::StepOps epaxos_step_ops(uint32_t N);
+}  // namespace pxs_lat
+static StepOps lat_step_ops_for(uint32_t protocol, uint32_t N, bool wlds, bool serial) {
+  if (serial) {
+    if (protocol == PAXISIM_WPAXOS) return pxs_lat::wpaxos_serial_step_ops(N, wlds);
+    if (protocol == PAXISIM_ABD) return pxs_lat::abd_serial_step_ops(N);
+    if (protocol == PAXISIM_EPAXOS) return pxs_lat::epaxos_serial_step_ops(N);
+    return pxs_lat::paxos_serial_step_ops(N);
+  }
+  if (protocol == PAXISIM_WPAXOS) return pxs_lat::wpaxos_step_ops(N, wlds);
+  if (protocol == PAXISIM_ABD) return pxs_lat::abd_step_ops(N);
+  if (protocol == PAXISIM_EPAXOS) return pxs_lat::epaxos_step_ops(N);
+  return pxs_lat::paxos_step_ops(N);
 }
 
 extern "C" int paxisim_create(const paxisim_config* cfg, const paxisim_workload* wl, const paxisim_fault_process* fp,
@@ -1822,7 +1856,127 @@ extern "C" int paxisim_occupancy(paxisim* h, int* blocks_per_cu, uint32_t* lds_b
 
 extern "C" int paxisim_device_bytes(paxisim* h, uint64_t* bytes) {
   if (!h || !bytes) return fail(PAXISIM_EINVAL, "null argument");
-  *bytes = h->arena_bytes;
+  *bytes = h->arena_bytes + h->lat_bytes;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Client request latency (include/paxisim.h, DESIGN.md §3.12, lat_kernel.h)
+// ---------------------------------------------------------------------------
+static size_t lat_acc_words(const Params& P) { return (size_t)LAT_SLICES * P.WK * lat_row(P.lat_bins); }
+
+extern "C" int paxisim_latency_enable(paxisim* h, uint32_t bins) {
+  if (!h) return fail(PAXISIM_EINVAL, "null handle");
+  if (bins < 16u || bins > PAXISIM_LAT_MAX_BINS || (bins & (bins - 1u)))
+    return fail(PAXISIM_EINVAL, "latency bins must be a power of two in [16, %u]", PAXISIM_LAT_MAX_BINS);
+  if (h->P.lat_bins) return fail(PAXISIM_EINVAL, "latency is already enabled");
+  if (h->t) return fail(PAXISIM_EINVAL, "latency can only be enabled before the first step");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  // the recording build of the handle's kernel: the same instance, so the launch shape chosen at create fits it
+  const StepOps ops = lat_step_ops_for(h->P.protocol, h->P.N, h->P.wlds != 0, h->ops.serial);
+  int vgprs = 0, maxthr = 0;
+  if (!ops.launch || ops.serial != h->ops.serial || ops.staged != h->ops.staged ||
+      ops.attrs(&vgprs, &maxthr) != hipSuccess || (!ops.serial && h->P.G * h->P.N * LANES > (uint32_t)maxthr))
+    return fail(PAXISIM_EUNSUPP, "no latency-recording build of this handle's step kernel");
+  Params P = h->P;
+  P.lat_bins = bins;
+  // every worker present at create issued its first request at step 0: the zeroed stamps
+  const size_t sb = sizeof(uint32_t) * P.WK * P.C, ab = sizeof(unsigned long long) * lat_acc_words(P);
+  const size_t ob = sizeof(unsigned long long) * P.WK * lat_row(bins);
+  unsigned long long* o = nullptr;
+  hipError_t e;
+  if ((e = hipMalloc(&P.lat_stamp, sb)) != hipSuccess || (e = hipMalloc(&P.lat_acc, ab)) != hipSuccess ||
+      (e = hipMalloc(&o, ob)) != hipSuccess || (e = hipMemsetAsync(P.lat_stamp, 0, sb, h->stream)) != hipSuccess ||
+      (e = hipMemsetAsync(P.lat_acc, 0, ab, h->stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(h->stream)) != hipSuccess) {
+    if (P.lat_stamp) (void)hipFree(P.lat_stamp);
+    if (P.lat_acc) (void)hipFree(P.lat_acc);
+    if (o) (void)hipFree(o);
+    return fail(PAXISIM_ENOMEM, "latency buffers (%zu bytes): %s", sb + ab + ob, hipGetErrorString(e));
+  }
+  h->P = P;
+  h->ops = ops;
+  h->lds_set = -1;        // the dynamic-LDS ceiling is per kernel
+  h->d_lat_out = o;
+  h->lat_bytes = sb + ab + ob;
+  return 0;
+}
+
+extern "C" int paxisim_latency_reset(paxisim* h) {
+  if (!h) return fail(PAXISIM_EINVAL, "null handle");
+  if (!h->P.lat_bins) return fail(PAXISIM_EINVAL, "latency is not enabled");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  // on the launch stream: after every step launched so far, before the next one
+  HIPCHK(hipMemsetAsync(h->P.lat_acc, 0, sizeof(unsigned long long) * lat_acc_words(h->P), h->stream));
+  return 0;
+}
+
+extern "C" int paxisim_latency_get(paxisim* h, uint32_t worker, paxisim_latency* out, uint64_t* hist) {
+  if (!h || !out) return fail(PAXISIM_EINVAL, "null argument");
+  if (!h->P.lat_bins) return fail(PAXISIM_EINVAL, "latency is not enabled");
+  if (worker != PAXISIM_ALL_WORKERS && worker >= h->P.WK) return fail(PAXISIM_EINVAL, "no worker %u", worker);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
+  const uint32_t bins = h->P.lat_bins;
+  const size_t row = lat_row(bins), n = (size_t)h->P.WK * row;
+  lat_reduce<<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(h->P, h->d_lat_out);
+  HIPCHK(hipGetLastError());
+  std::vector<unsigned long long> acc(n);
+  HIPCHK(hipMemcpyAsync(acc.data(), h->d_lat_out, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  memset(out, 0, sizeof *out);
+  out->bins = bins;
+  out->min = 0xFFFFFFFFu;
+  if (hist) memset(hist, 0, sizeof(uint64_t) * bins);
+  for (uint32_t w = 0; w < h->P.WK; w++) {
+    if (worker != PAXISIM_ALL_WORKERS && w != worker) continue;
+    const unsigned long long* a = acc.data() + (size_t)w * row;
+    uint64_t cnt = a[bins + LAT_OVF];
+    for (uint32_t b = 0; b < bins; b++) {
+      cnt += a[b];
+      if (hist) hist[b] += a[b];
+    }
+    out->count += cnt;
+    out->sum += a[bins + LAT_SUM];
+    out->overflow += a[bins + LAT_OVF];
+    if (cnt) {
+      out->min = std::min(out->min, 0xFFFFFFFFu - (uint32_t)a[bins + LAT_NMIN]);
+      out->max = std::max(out->max, (uint32_t)a[bins + LAT_MAX]);
+    }
+  }
+  return 0;
+}
+
+extern "C" int paxisim_latency_stat_of(const paxisim_latency* l, const uint64_t* hist, double step_ms,
+                                       paxisim_latency_stat* out) {
+  if (!l || !hist || !out) return fail(PAXISIM_EINVAL, "null argument");
+  if (l->bins > PAXISIM_LAT_MAX_BINS) return fail(PAXISIM_ERANGE, "bins exceeds PAXISIM_LAT_MAX_BINS");
+  if (l->count == 0) return fail(PAXISIM_EINVAL, "no samples");
+  memset(out, 0, sizeof *out);
+  out->size = l->count;
+  out->mean = (double)l->sum * step_ms / (double)l->count;
+  out->min = l->min * step_ms;
+  out->max = l->max * step_ms;
+  out->exact = 1;
+  // stat.go:44-66: element int(p * size) of the sorted samples
+  const double ps[4] = {0.5, 0.95, 0.99, 0.999};
+  double* dst[4] = {&out->median, &out->p95, &out->p99, &out->p999};
+  for (int k = 0; k < 4; k++) {
+    uint64_t idx = (uint64_t)(ps[k] * (double)l->count);
+    if (idx >= l->count) idx = l->count - 1;
+    uint64_t cum = 0;
+    uint32_t b = 0;
+    for (; b < l->bins; b++) {
+      cum += hist[b];
+      if (idx < cum) break;
+    }
+    if (b < l->bins) {
+      *dst[k] = b * step_ms;
+    } else {                      // inside the overflow bin: only its bounds are known
+      *dst[k] = out->max;
+      out->exact = 0;
+    }
+  }
   return 0;
 }
 

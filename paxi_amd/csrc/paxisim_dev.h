@@ -17,6 +17,20 @@
 
 #include "../../include/paxisim.h"
 
+// PXS_LAT = 1 builds a kernel unit that records client request latency
+// (lat_kernel.h).  Every k_*.hip unit is built twice (__graft_entry__.LAT_FLAGS):
+// the default units carry no latency code at all, and a handle switches to the
+// recording ones at paxisim_latency_enable.  Off and on by a wave-uniform branch
+// in shared units cost config 2 2.2-3.5% with latency off.  The
+// recording units keep every name apart from the default ones' in namespace
+// pxs_lat; the types are the same declarations, so their layouts are equal.
+#ifndef PXS_LAT
+#define PXS_LAT 0
+#endif
+#if PXS_LAT
+#define pxs pxs_lat
+#endif
+
 namespace pxs {
 
 constexpr uint32_t PMAX = 32;   // pending requests per replica (p.requests)
@@ -211,6 +225,10 @@ struct Params {
   uint32_t* kv_val;      // [K][r][C] value = command id of the last write, 0 = nil
   uint32_t* kv_ver;      // [r][C] database.version
   uint32_t* wrep;        // [WK][C] Reply.Value of each worker's last reply (0 = nil)
+  // client request latency (lat_kernel.h); off while lat_bins == 0
+  uint32_t lat_bins;             // one-step histogram bins per worker
+  uint32_t* lat_stamp;           // [WK][C] issue step of each worker's request in flight
+  unsigned long long* lat_acc;   // [LAT_SLICES][WK][lat_bins + LAT_EXTRA] accumulators
 };
 
 // Persistent scalars of the kpaxos instance (blk, k, r, lane) in the record

@@ -12,6 +12,7 @@
 //   static void client_request(P, x, cid)       the HTTP request path (http.go:99)
 #pragma once
 #include "paxisim_dev.h"
+#include "lat_kernel.h"
 
 namespace pxs {
 
@@ -449,6 +450,7 @@ __device__ __forceinline__ void client_reply(const Params& P, Rep<NT>& x, uint32
   const uint32_t wi = (w << 6) | x.lane;
   if (x.l_wcur[wi] != cid) return;              // duplicate reply: the worker moved on
   x.replies++;
+  if (PXS_LAT) lat_sample(P, x.blk, x.lane, w, x.c, x.t);   // the recording units only (lat_kernel.h)
   if (PXS_REPLY_STORE && PXS_REPLY_DEFER) {
     reply_flush<NT>(P, x);
     x.rw = w + 1u;
@@ -466,6 +468,7 @@ __device__ __forceinline__ void client_reply(const Params& P, Rep<NT>& x, uint32
     }
     x.l_wiss[wi] = issued + 1u;
     x.l_wcur[wi] = (uint32_t)nc;
+    if (PXS_LAT) lat_issue(P, w, x.c, x.t);
     uint32_t b = x.b0 + 1u;
     if (b >= P.D) b -= P.D;
     const uint32_t box = (b * nrep<NT>(P) + P.target[w]) * P.NS + nrep<NT>(P);
@@ -493,6 +496,7 @@ __device__ __forceinline__ void client_start(const Params& P, Rep<NT>& x) {
     const uint32_t wi = (w << 6) | x.lane;
     x.l_wcur[wi] = 1u + w;
     x.l_wiss[wi] = 1u;
+    if (PXS_LAT) lat_issue(P, w, x.c, x.t);
     const uint32_t box = (x.b0 * nrep<NT>(P) + x.r) * P.NS + nrep<NT>(P);
     uint8_t* cp = &x.l_cnt[(box << 6) | x.lane];
     const uint32_t k = *cp;

@@ -47,6 +47,26 @@ def reduce_counters(values, elapsed, device=None, group=None):
     return dict(zip(COUNTERS, vec.tolist())), tim.tolist()
 
 
+def reduce_latency(hist, group=None, device=None):
+    """Sum a latency.Histogram over all ranks (counts, count, sum and overflow
+    add; min of min, max of max): the job's histogram on every rank.  The same
+    tensor path as reduce_counters; no-op without a process group."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    from .latency import Histogram
+    add = torch.tensor([int(v) for v in hist.counts] + [hist.count, hist.sum, hist.overflow], dtype=torch.int64,
+                       device=device)
+    lo = torch.tensor([hist.min], dtype=torch.int64, device=device)
+    hi = torch.tensor([hist.max], dtype=torch.int64, device=device)
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(add, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=group)
+        dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=group)
+    add = add.tolist()
+    return Histogram(np.array(add[:-3], dtype=np.uint64), add[-3], add[-2], add[-1], int(lo.item()), int(hi.item()))
+
+
 def stats_counters(delta, alg_bytes=0, violations=0, flagged=None, **extra):
     """Counter dict from a stats delta (bench.stats_delta), scan results and
     extra integer counters (agree_compared, agree_missed, active, active_start)."""

@@ -82,6 +82,17 @@ def load_library():
     L.paxisim_dist_destroy.argtypes = [C.c_void_p]
     L.paxisim_commands.restype = C.c_int
     L.paxisim_commands.argtypes = [C.c_void_p, C.c_uint64, P(C.c_uint32), C.c_uint32, P(C.c_uint32), P(C.c_uint32)]
+    # client request latency (ABI v14); a library built from older sources (the miscompile guard's
+    # pinned reproducers, __graft_entry__.GUARDS) has none of it, and Simulation.latency* then raise
+    if hasattr(L, "paxisim_latency_enable"):
+        L.paxisim_latency_enable.restype = C.c_int
+        L.paxisim_latency_enable.argtypes = [C.c_void_p, C.c_uint32]
+        L.paxisim_latency_reset.restype = C.c_int
+        L.paxisim_latency_reset.argtypes = [C.c_void_p]
+        L.paxisim_latency_get.restype = C.c_int
+        L.paxisim_latency_get.argtypes = [C.c_void_p, C.c_uint32, P(abi.Latency), P(C.c_uint64)]
+        L.paxisim_latency_stat_of.restype = C.c_int
+        L.paxisim_latency_stat_of.argtypes = [P(abi.Latency), P(C.c_uint64), C.c_double, P(abi.LatencyStat)]
     if L.paxisim_abi_version() != abi.ABI_VERSION:
         raise PaxisimError("ABI version mismatch between paxi_amd/abi.py and libpaxisim.so")
     _lib = L
@@ -99,7 +110,8 @@ EXPORTED = ["paxisim_abi_version", "paxisim_build_id", "paxisim_last_error", "pa
             "paxisim_linearizable", "paxisim_history", "paxisim_occupancy", "paxisim_inject", "paxisim_read_log",
             "paxisim_history_load", "paxisim_active_clusters", "paxisim_read_activity", "paxisim_read_client", "paxisim_quorum", "paxisim_dist_init", "paxisim_dist_unique_id",
             "paxisim_dist_init_rank", "paxisim_dist_allreduce", "paxisim_dist_stats", "paxisim_dist_destroy",
-            "paxisim_read_kv", "paxisim_read_inbox", "paxisim_deliver", "paxisim_commands"]
+            "paxisim_read_kv", "paxisim_read_inbox", "paxisim_deliver", "paxisim_commands",
+            "paxisim_latency_enable", "paxisim_latency_reset", "paxisim_latency_get", "paxisim_latency_stat_of"]
 
 
 def _check(rc):
@@ -257,6 +269,33 @@ class Simulation:
         b = C.c_uint64()
         _check(load_library().paxisim_device_bytes(self.h, C.byref(b)))
         return b.value
+
+    # client request latency (stat.go, benchmark.go:186)
+    @staticmethod
+    def _lat(name):
+        fn = getattr(load_library(), name, None)
+        if fn is None:
+            raise PaxisimError(f"{LIB_PATH} was built without {name} (client request latency, ABI v14)")
+        return fn
+
+    def latency_enable(self, bins=256):
+        """Record every worker's request latency from now on, in `bins` one-step
+        bins (a power of two in [16, abi.LAT_MAX_BINS]); before the first step only."""
+        _check(self._lat("paxisim_latency_enable")(self.h, bins))
+
+    def latency_reset(self):
+        """Forget the samples so far (a warm-up); requests in flight keep their issue step."""
+        _check(self._lat("paxisim_latency_reset")(self.h))
+
+    def latency(self, worker=None):
+        """The latency.Histogram of one worker, or of all workers (worker=None)."""
+        from .latency import Histogram
+        lat = abi.Latency()
+        fn = self._lat("paxisim_latency_get")
+        w = abi.ALL_WORKERS if worker is None else worker
+        hist = (C.c_uint64 * abi.LAT_MAX_BINS)()
+        _check(fn(self.h, w, C.byref(lat), hist))
+        return Histogram(hist[:lat.bins], lat.count, lat.sum, lat.overflow, lat.min, lat.max)
 
     def close(self):
         if self.h:

@@ -17,6 +17,10 @@ pids=()
 for s in $SRCS; do
   /opt/rocm/bin/hipcc $(tuflags "$s") "$@" -c -o "$OBJ/${s%.hip}.o" "paxi_amd/csrc/$s" &
   pids+=($!)
+  if [[ $s == k_* ]]; then   # and the unit's latency-recording build (__graft_entry__.LAT_FLAGS)
+    /opt/rocm/bin/hipcc $(tuflags "$s") "$@" -DPXS_LAT=1 -c -o "$OBJ/${s%.hip}_lat.o" "paxi_amd/csrc/$s" &
+    pids+=($!)
+  fi
 done
 for p in "${pids[@]}"; do wait "$p"; done
 # the variant's own build id: the sources' fingerprint + its extra flags

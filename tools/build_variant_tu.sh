@@ -24,6 +24,7 @@ for s in $SRCS; do
   else
     objs+=("build/hip/${s%.hip}.o")
   fi
+  if [[ $s == k_* ]]; then objs+=("build/hip/${s%.hip}_lat.o"); fi   # the product's latency-recording units, as built
 done
 for p in "${pids[@]}"; do wait "$p"; done
 # the variant's own build id: the sources' fingerprint + its extra flags
