@@ -525,7 +525,7 @@ __device__ void swap_slots(const Params& P, uint64_t p, uint64_t q, uint32_t j) 
   for (uint32_t r = 0; r < N; r++) {
     const size_t ip = (size_t)r * C + p, iq = (size_t)r * C + q;
     const uint32_t np0 = P.npend[ip] & NPEND_MASK, np1 = P.npend[iq] & NPEND_MASK;
-    const uint32_t nf0 = P.nfwd[ip], nf1 = P.nfwd[iq];
+    const uint32_t nf0 = P.nfwd[ip] & NFWD_MASK, nf1 = P.nfwd[iq] & NFWD_MASK;
     const bool gh = ((P.flags[ip] | P.flags[iq]) & PAXISIM_F_GHOST) != 0u;
     const uint32_t np = np0 > np1 ? np0 : np1, nf = nf0 > nf1 ? nf0 : nf1;
     // lane j < 32: pending entry j, 32 <= j < 64: forwards entry j - 32 (PMAX = FMAX = 32)
@@ -541,7 +541,7 @@ __device__ void swap_slots(const Params& P, uint64_t p, uint64_t q, uint32_t j) 
     if (a) { a[p] = vq; a[q] = vp; }
     if (g) { g[p] = gq; g[q] = gp; }
   }
-  swap_rows(P.ballot, 7 * N, C, p, q, j);        // ballot slot execute meta flags npend (+ committed bits) nfwd
+  swap_rows(P.ballot, 7 * N, C, p, q, j);        // ballot slot execute meta flags npend (+ committed bits) nfwd (+ exists bits)
   swap_rows(P.digest, N, C, p, q, j);
   swap_rows(P.kc, 1, C, p, q, j);
   swap_rows(P.link_drop, 2 * N * N, C, p, q, j);   // link_drop then link_slow

@@ -38,6 +38,13 @@ constexpr uint32_t FMAX = 32;   // forwards table per replica (node.forwards)
 // Params::npend holds the count in its low half; the high half carries a packed Multi-Paxos
 // window's committed bits (paxos_kernel.h cm_note), so every reader of the row masks it
 constexpr uint32_t NPEND_MASK = 0xFFFFu;
+// Params::nfwd likewise: the count (<= FMAX) in the low half, the window's exists bits in the high
+// half.  Bit 1 of Params::meta, between `active` and the phase-1 acks, is the
+// replica's sticky "a flags word with a request or a quorum object was written here" bit; in
+// registers it rides in a spare bit of Rep::iflags.
+constexpr uint32_t NFWD_MASK = 0xFFFFu;
+constexpr uint32_t META_REQST = 1u << 1;
+constexpr uint32_t IF_REQST = 1u << 31;
 // Which serial Multi-Paxos units keep their windows as packed 16-B entries (paxos_kernel.h): all but
 // the 9-replica one.  Config 2's lanes sit at scattered slots, where one 16-B piece per lane replaces
 // three scattered words (+7.7%); config 4's clusters run in lockstep, its plane rows are read whole,

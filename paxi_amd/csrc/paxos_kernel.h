@@ -94,10 +94,29 @@ __device__ __forceinline__ void set_a(Rep<NT>& x, uint32_t i, uint32_t v) {
 // committed-entry bits of a packed window: exec() stops at the first clear bit
 // without reading the entry (W <= 16; wider windows read it).  Every write of
 // an entry's flags word comes through here (set_b, eput).
+//
+// Multi-Paxos keeps the committed bits in the low half of cmask and, in the
+// high half, one exists bit per slot (set exactly when the flags word has
+// EF_EXISTS), and a sticky bit per replica (IF_REQST in iflags) that is set
+// when a flags word with a quorum object or a request is written and never
+// cleared.  While it is clear the two bits of a slot are its whole flags word
+// up to the command, so a follower's HandleP2a on a fresh slot and HandleP3
+// need no read of the entry (win_bits).
 template <int NT>
 __device__ __forceinline__ void cm_note(Rep<NT>& x, uint32_t i, uint32_t c) {
-  const uint32_t bit = 1u << ((per_key(x) ? i >> 2 : (i - x.e0) >> 8) & 31u);
-  x.cmask = (c & EF_COMMIT) ? (x.cmask | bit) : (x.cmask & ~bit);
+  if (per_key(x)) {
+    const uint32_t bit = 1u << ((i >> 2) & 31u);
+    x.cmask = (c & EF_COMMIT) ? (x.cmask | bit) : (x.cmask & ~bit);
+    return;
+  }
+  const uint32_t w = ((i - x.e0) >> 8) & 15u;
+  x.cmask = (x.cmask & ~(0x10001u << w)) | (((c & EF_COMMIT) ? 1u : 0u) << w) | (((c & EF_EXISTS) ? 0x10000u : 0u) << w);
+  x.iflags |= (c & (EF_QUORUM | EF_REQSELF | EF_REQEXT)) ? IF_REQST : 0u;
+}
+// the window's exists / committed bits describe its slots (the packed Multi-Paxos units, W <= 16)
+template <int NT>
+__device__ __forceinline__ bool win_bits(const Params& P, const Rep<NT>& x) {
+  return packed_log(x) && !per_key(x) && P.W <= 16u;
 }
 template <int NT>
 __device__ __forceinline__ void set_b(Rep<NT>& x, uint32_t i, uint32_t v) {
@@ -633,7 +652,9 @@ __device__ __forceinline__ void paxos_handle_p2a(const Params& P, Rep<NT>& x, ui
     if (ms > x.slot) x.slot = ms;
     if (in_window<NT>(P, x, ms)) {
       const uint32_t i = eidx<NT>(P, x, ms);
-      Ent e = eget<NT>(x, i);
+      // a slot whose exists bit is clear holds nothing the new entry keeps: no read
+      Ent e{0u, 0u, 0u};
+      if (!win_bits<NT>(P, x) || ((x.cmask >> (16u + ((uint32_t)ms & (P.W - 1u)))) & 1u)) e = eget<NT>(x, i);
       if (e.c & EF_EXISTS) {
         if (!(e.c & EF_COMMIT) && mb > e.b) {
           if ((e.c & CMD_MASK) != mcid && (e.c & (EF_REQSELF | EF_REQEXT))) {
@@ -709,7 +730,15 @@ __device__ __forceinline__ void paxos_handle_p3(const Params& P, Rep<NT>& x, uin
   if (ms > x.slot) x.slot = ms;
   if (in_window<NT>(P, x, ms)) {
     const uint32_t i = eidx<NT>(P, x, ms);
-    uint32_t c = eb(x, i);
+    uint32_t c;
+    if (win_bits<NT>(P, x) && !(x.iflags & IF_REQST)) {
+      // no entry here ever held a request or a quorum object: the slot's two bits are its
+      // flags, and its old command is overwritten whatever it was - no read
+      const uint32_t m = x.cmask >> ((uint32_t)ms & (P.W - 1u));
+      c = (m & 0x10000u ? EF_EXISTS : 0u) | (m & 1u ? EF_COMMIT : 0u);
+    } else {
+      c = eb(x, i);
+    }
     if (c & EF_EXISTS) {
       if ((c & CMD_MASK) != mcid && (c & (EF_REQSELF | EF_REQEXT))) {
         node_forward<NT>(P, x, bal_id(mb), ereq<NT>(P, x, i, c));
@@ -795,14 +824,15 @@ struct PaxosProto {
     const uint32_t meta = P.meta[i];
     x.active = meta & 1u;
     x.p1mask = meta >> 16;
-    // the committed-window bits of a packed window ride in the spare half of the npend row
-    const uint32_t np = P.npend[i];
+    // the committed bits of a packed window ride in the spare half of the npend row, its exists
+    // bits in the spare half of the nfwd row, the sticky request-state bit in bit 1 of meta
+    const uint32_t np = P.npend[i], nf = P.nfwd[i];
     x.npend = np & NPEND_MASK;
-    x.cmask = np >> 16;
-    x.nfwd = P.nfwd[i];
+    x.nfwd = nf & NFWD_MASK;
+    x.cmask = (np >> 16) | (nf & ~NFWD_MASK);
     x.digest = P.digest[i];
     // the replica's one instance: log window [r][W][lane], SoA pending table
-    x.iflags = x.flags & (PAXISIM_F_WOVF | PAXISIM_F_GHOST);
+    x.iflags = (x.flags & (PAXISIM_F_WOVF | PAXISIM_F_GHOST)) | ((meta & META_REQST) ? IF_REQST : 0u);
     x.inst = x.r;
     x.key = 0;
     x.ktag = 0;
@@ -831,9 +861,9 @@ struct PaxosProto {
     P.ballot[i] = x.ballot;
     P.slot[i] = (uint32_t)x.slot;
     P.execute[i] = (uint32_t)x.execute;
-    P.meta[i] = (x.active & 1u) | (x.p1mask << 16);
+    P.meta[i] = (x.active & 1u) | ((x.iflags & IF_REQST) ? META_REQST : 0u) | (x.p1mask << 16);
     P.npend[i] = packed_log(x) ? x.npend | (x.cmask << 16) : x.npend;
-    P.nfwd[i] = x.nfwd;
+    P.nfwd[i] = packed_log(x) ? x.nfwd | (x.cmask & ~NFWD_MASK) : x.nfwd;
     P.digest[i] = x.digest;
   }
   template <int NT>
