@@ -514,6 +514,45 @@ int  paxisim_latency_get(paxisim* h, uint32_t worker, paxisim_latency* out, uint
 int  paxisim_latency_stat_of(const paxisim_latency* l, const uint64_t* hist, double step_ms,
                              paxisim_latency_stat* out);
 
+/* ---- Client-side op history of every protocol (benchmark.go:246-275,
+ * history.go).  Where a latency sample is taken, worker w
+ * also records the op {key, is_write, value, start, end}: key and is_write
+ * are those of the answered command id (paxisim_commands; a key beyond the key
+ * space is the last index, as at the replicas), value is the command id for a
+ * write (op.input) and the reply's value for a read (op.output; 0 = a read of
+ * nil), start is the step the worker issued the request (start_step[w] for its
+ * first), end the step of the accepted reply.  So the ops recorded and dropped
+ * add up to paxisim_stats.replies: a late worker's start, a reply to an
+ * injected command id and a request never answered are no ops.  With
+ * reply_when_commit the replies carry no value (as in the reference) and every
+ * read is recorded with value 0.  A cluster's history is worker 0's ops in
+ * completion order, then worker 1's, ... (the canonical order).
+ * paxisim_linearizable and paxisim_history* are not changed by any of this:
+ * they remain ABD's replica-side history. */
+#define PAXISIM_CLIENT_HISTORY_MAX (1u << 20)
+/* Start recording, ops_per_worker ops per worker and cluster (in [1,
+ * PAXISIM_CLIENT_HISTORY_MAX]); a worker's later ops are counted, not kept,
+ * and raise no flag.  Once, before the first step and after
+ * paxisim_latency_enable, whose step kernels and issue stamps it uses (EINVAL
+ * otherwise).  EUNSUPP on a handle other than ABD with config.kv == 0: its
+ * replies carry no read values.  ENOMEM: the buffer is outstanding x clusters
+ * (rounded up to 64) x ops_per_worker x 16 bytes, which bounds ops_per_worker
+ * at bench scale (2^20 clusters x 8 workers x 64 ops = 8 GiB). */
+int  paxisim_client_history_enable(paxisim* h, uint32_t ops_per_worker);
+/* The ops of one local cluster in canonical order, 5 words per op {key,
+ * is_write, value, start step, end step}: at most cap_ops are written (buf may
+ * be NULL), *n_out is the number recorded, *dropped_out (may be NULL) the ops
+ * past ops_per_worker.  EINVAL when the history is not enabled. */
+int  paxisim_client_history(paxisim* h, uint64_t cluster, uint32_t* buf, uint32_t cap_ops,
+                            uint32_t* n_out, uint32_t* dropped_out);
+/* History.ReadFile into the device: replace the ops of one worker of a local
+ * cluster with n ops in the format of paxisim_client_history (n <=
+ * ops_per_worker; key < keys and is_write <= 1, else EINVAL). */
+int  paxisim_client_history_load(paxisim* h, uint64_t cluster, uint32_t worker, const uint32_t* ops, uint32_t n);
+/* History.Linearizable over every (cluster, key) of the client histories:
+ * anomalous reads, ops checked, partitions skipped (paxisim_linearizable). */
+int  paxisim_client_linearizable(paxisim* h, uint64_t* anomalies, uint64_t* ops, uint64_t* skipped);
+
 /* ---- Multi-GPU: clusters shard by range over handles
  * (paxisim_config.cluster_base = rank * clusters), the simulation itself has
  * no collective, and totals are reduced with RCCL (opened at run time:

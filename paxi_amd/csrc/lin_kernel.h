@@ -737,43 +737,67 @@ __device__ inline void lin_sort(const uint4* src, uint32_t n, LinScratch& s) {
   if (G) __threadfence_block();
 }
 
-// Canonical op index -> its history record (replica-major; len[r] ops each).
+// The history a scan reads.  A source type S supplies, per cluster, sources()
+// sequences of at most per_source() records (at most MAX_SRC of them), the
+// length of each, a record's address, and - given the cluster's context word
+// ctx() - the key of a record's first word and the record as the checker's op
+// {key | write << 31, value, start, end}.  The canonical order is source-major.
+// LinAbd: the replicas' completed ops (abd_kernel.h), records already ops.
+// chist_kernel.h LinClient: the workers' ops of any protocol.
+struct LinAbd {
+  static constexpr uint32_t MAX_SRC = PAXISIM_MAX_N;
+  __host__ __device__ static uint32_t sources(const Params& P) { return P.N; }
+  __host__ __device__ static uint32_t per_source(const Params& P) { return P.H; }
+  __device__ static uint32_t ctx(const Params&, uint64_t) { return 0u; }
+  __device__ static uint32_t len(const Params& P, uint32_t s, uint64_t c) { return P.execute[rc(P, s, c)]; }
+  __device__ static const uint4* at(const Params& P, uint32_t s, uint64_t c, uint32_t idx) {
+    return &P.hist[((size_t)s * P.C + c) * P.H + idx];
+  }
+  __device__ static uint32_t key(const Params&, uint32_t, uint32_t x) { return x & 0x7FFFFFFFu; }
+  __device__ static const uint4& op(const Params&, uint32_t, const uint4& o) { return o; }
+};
+
+// Canonical op index -> its history record (source-major; len[s] ops each).
+template <class S>
 __device__ __forceinline__ const uint4* hist_at(const Params& P, uint64_t c, const uint32_t* len, uint32_t idx) {
   uint32_t r = 0;
   while (idx >= len[r]) idx -= len[r++];
-  return &P.hist[((size_t)r * P.C + c) * P.H + idx];
+  return S::at(P, r, c, idx);
 }
 
 // grid: one workgroup (LIN_LW waves) per cluster c0 + blockIdx.x.  stage:
-// [grid][N*H] ops, the cluster's history grouped by key (its own region of
+// [grid][sources * per_source] ops, the cluster's history grouped by key (its own region of
 // the launch's workspace).  Dynamic LDS: LIN_LW sort buffers (LIN_SORT_BYTES);
 // partitions of at most LIN_SMAX ops are checked in registers (LinReg).
+template <class S>
 __global__ void __launch_bounds__(LIN_LW * 64, PXS_LIN_MINW) lin_cluster_kernel(Params P, uint64_t c0, uint4* stage_all,
                                                                    unsigned long long* out, uint2* big) {
   extern __shared__ uint4 lds_lin[];
-  __shared__ uint32_t len[PAXISIM_MAX_N];
+  __shared__ uint32_t len[S::MAX_SRC];
   __shared__ uint32_t cnt[LIN_LW][PAXISIM_MAX_KEYS];   // per wave slice, per key
   __shared__ uint32_t koff[PAXISIM_MAX_KEYS + 1];
   const uint64_t c = c0 + blockIdx.x;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t K = P.keys;
-  const uint32_t cap = P.N * P.H;
+  const uint32_t NS = S::sources(P);
+  const uint32_t cap = NS * S::per_source(P);
+  const uint32_t cx = S::ctx(P, c);
   uint4* stage = stage_all + (size_t)blockIdx.x * cap;
   uint8_t* wsp = reinterpret_cast<uint8_t*>(lds_lin) + wave * LIN_SORT_BYTES;
 #ifdef PXS_LIN_STAMPS
   uint32_t lst[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
   LIN_T0(tp1)
-  if (threadIdx.x < P.N) len[threadIdx.x] = P.execute[rc(P, threadIdx.x, c)];
+  if (threadIdx.x < NS) len[threadIdx.x] = S::len(P, threadIdx.x, c);
   for (uint32_t k = threadIdx.x; k < LIN_LW * PAXISIM_MAX_KEYS; k += blockDim.x) (&cnt[0][0])[k] = 0;
   __syncthreads();
   uint32_t tot = 0;
-  for (uint32_t r = 0; r < P.N; r++) tot += len[r];
+  for (uint32_t r = 0; r < NS; r++) tot += len[r];
   // pass 1: per-key counts of each wave's slice of the canonical sequence (key words only)
   const uint32_t per = (tot + LIN_LW - 1u) / LIN_LW;
   const uint32_t lo = wave * per < tot ? wave * per : tot, hi = lo + per < tot ? lo + per : tot;
   for (uint32_t i = lo + lane_id(); i < hi; i += 64u) {
-    const uint32_t key = *reinterpret_cast<const uint32_t*>(hist_at(P, c, len, i)) & 0x7FFFFFFFu;
+    const uint32_t key = S::key(P, cx, *reinterpret_cast<const uint32_t*>(hist_at<S>(P, c, len, i)));
     if (key < K) atomicAdd(&cnt[wave][key], 1u);       // (paxisim_history_load admits keys < K only)
   }
   __syncthreads();
@@ -797,7 +821,7 @@ __global__ void __launch_bounds__(LIN_LW * 64, PXS_LIN_MINW) lin_cluster_kernel(
   // rank among the chunk's ops of that key (a ballot per distinct key).
   for (uint32_t i0 = lo; i0 < hi; i0 += 64u) {
     const uint32_t i = i0 + lane_id();
-    const uint4 o = i < hi ? *hist_at(P, c, len, i) : make_uint4(0u, 0u, 0u, 0u);
+    const uint4 o = i < hi ? S::op(P, cx, *hist_at<S>(P, c, len, i)) : make_uint4(0u, 0u, 0u, 0u);
     const bool act = i < hi && (o.x & 0x7FFFFFFFu) < K;
     const uint32_t key = act ? (o.x & 0x7FFFFFFFu) : 0xFFFFFFFFu;
     uint64_t todo = __ballot(act);

@@ -18,6 +18,7 @@
 #include <vector>
 
 #define PXS_LAT_REDUCE   // this unit defines and launches lat_reduce (lat_kernel.h)
+#define PXS_CHIST_READ   // and chist_read_kernel (chist_kernel.h)
 #include "epaxos_kernel.h"
 #include "lin_kernel.h"
 #include "paxisim_dev.h"
@@ -76,6 +77,7 @@ struct paxisim {
   // client request latency (lat_kernel.h): P.lat_stamp, P.lat_acc and the folded readout [WK][bins + LAT_EXTRA]
   unsigned long long* d_lat_out = nullptr;
   size_t lat_bytes = 0;
+  size_t ch_bytes = 0;             // client-side op history (chist_kernel.h): P.ch_ops and P.ch_cnt
 };
 
 static inline size_t rc_host(const Params& P, uint32_t r, uint64_t c) { return (size_t)r * P.C + c; }
@@ -936,6 +938,8 @@ extern "C" int paxisim_destroy(paxisim* h) {
   if (h->P.lat_stamp) (void)hipFree(h->P.lat_stamp);
   if (h->P.lat_acc) (void)hipFree(h->P.lat_acc);
   if (h->d_lat_out) (void)hipFree(h->d_lat_out);
+  if (h->P.ch_ops) (void)hipFree(h->P.ch_ops);
+  if (h->P.ch_cnt) (void)hipFree(h->P.ch_cnt);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return 0;
@@ -1856,7 +1860,7 @@ extern "C" int paxisim_occupancy(paxisim* h, int* blocks_per_cu, uint32_t* lds_b
 
 extern "C" int paxisim_device_bytes(paxisim* h, uint64_t* bytes) {
   if (!h || !bytes) return fail(PAXISIM_EINVAL, "null argument");
-  *bytes = h->arena_bytes + h->lat_bytes;
+  *bytes = h->arena_bytes + h->lat_bytes + h->ch_bytes;
   return 0;
 }
 
@@ -2034,19 +2038,19 @@ extern "C" int paxisim_history_load(paxisim* h, uint64_t cluster, uint32_t repli
   return 0;
 }
 
-extern "C" int paxisim_linearizable(paxisim* h, uint64_t* anomalies, uint64_t* ops, uint64_t* skipped) {
-  if (!h) return fail(PAXISIM_EINVAL, "null handle");
-  if (h->P.protocol != PAXISIM_ABD || h->P.H == 0)
-    return fail(PAXISIM_EUNSUPP, "linearizability scan needs protocol ABD with history > 0");
+// History.Linearizable over the history source S of every cluster (lin_kernel.h): LinAbd, the
+// replicas' completed ABD ops, or LinClient, the workers' ops of any protocol (chist_kernel.h).
+template <class S>
+static int lin_scan(paxisim* h, uint64_t* anomalies, uint64_t* ops, uint64_t* skipped) {
   HIPCHK(hipSetDevice(h->cfg.device));
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   HIPCHK(hipStreamSynchronize(h->stream));
   const Params& P = h->P;
-  // clusters per launch: each gets a stage of N*H ops (its history grouped by key).
+  // clusters per launch: each gets a stage of sources * per_source ops (ABD: N*H; its history grouped by key).
   // The stage takes up to a quarter of the free HBM (2-16 GiB): fewer, longer
   // launches leave less of each launch's last round of workgroups idle
   // (config 3: 21 -> 6 launches); PAXISIM_LIN_STAGE_MB overrides (A/B).
-  const size_t cap = (size_t)P.N * P.H;
+  const size_t cap = (size_t)S::sources(P) * S::per_source(P);
   size_t budget = 2ull << 30, freeb = 0, totb = 0;
   if (hipMemGetInfo(&freeb, &totb) == hipSuccess) budget = std::max(budget, std::min<size_t>(freeb / 4, 16ull << 30));
   if (const char* e = getenv("PAXISIM_LIN_STAGE_MB")) budget = std::max<size_t>(1, (size_t)atoll(e)) << 20;
@@ -2072,7 +2076,7 @@ extern "C" int paxisim_linearizable(paxisim* h, uint64_t* anomalies, uint64_t* o
   for (uint64_t c0 = 0; e == hipSuccess && c0 < P.clusters; c0 += chunk) {
     const uint64_t nc = std::min<uint64_t>(chunk, P.clusters - c0);
     if ((e = hipMemsetAsync(out + LIN_BIG, 0, 2 * sizeof(unsigned long long), h->stream)) != hipSuccess) break;
-    lin_cluster_kernel<<<(unsigned)nc, LIN_LW * 64, lds, h->stream>>>(P, c0, stage, out, big);
+    lin_cluster_kernel<S><<<(unsigned)nc, LIN_LW * 64, lds, h->stream>>>(P, c0, stage, out, big);
     unsigned long long bc[2] = {0, 0};
     if ((e = hipGetLastError()) != hipSuccess) break;
     if ((e = hipMemcpyAsync(bc, out + LIN_BIG, sizeof bc, hipMemcpyDeviceToHost, h->stream)) != hipSuccess) break;
@@ -2114,6 +2118,120 @@ extern "C" int paxisim_linearizable(paxisim* h, uint64_t* anomalies, uint64_t* o
   if (ops) *ops = res[LIN_OPS];
   if (skipped) *skipped = res[LIN_SKIP];   // partitions above LIN_VMAX ops (not checked)
   return 0;
+}
+
+extern "C" int paxisim_linearizable(paxisim* h, uint64_t* anomalies, uint64_t* ops, uint64_t* skipped) {
+  if (!h) return fail(PAXISIM_EINVAL, "null handle");
+  if (h->P.protocol != PAXISIM_ABD || h->P.H == 0)
+    return fail(PAXISIM_EUNSUPP, "linearizability scan needs protocol ABD with history > 0");
+  return lin_scan<LinAbd>(h, anomalies, ops, skipped);
+}
+
+// ---------------------------------------------------------------------------
+// Client-side op history of every protocol (include/paxisim.h, DESIGN.md §3.13, chist_kernel.h)
+// ---------------------------------------------------------------------------
+extern "C" int paxisim_client_history_enable(paxisim* h, uint32_t ops_per_worker) {
+  if (!h) return fail(PAXISIM_EINVAL, "null handle");
+  if (ops_per_worker == 0 || ops_per_worker > PAXISIM_CLIENT_HISTORY_MAX)
+    return fail(PAXISIM_EINVAL, "ops_per_worker must be in [1, %u]", PAXISIM_CLIENT_HISTORY_MAX);
+  if (h->P.ch_cap) return fail(PAXISIM_EINVAL, "the client history is already enabled");
+  if (h->t) return fail(PAXISIM_EINVAL, "the client history can only be enabled before the first step");
+  if (!h->P.lat_bins)
+    return fail(PAXISIM_EINVAL, "the client history needs the recording step kernels and their issue stamps: "
+                                "call paxisim_latency_enable first");
+  if (h->P.protocol != PAXISIM_ABD && !h->P.kv)
+    return fail(PAXISIM_EUNSUPP, "replies carry no read values (config.kv = 0)");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  Params P = h->P;
+  P.ch_cap = ops_per_worker;
+  const size_t cb = sizeof(uint32_t) * P.WK * P.C, ob = sizeof(uint4) * P.WK * P.C * (size_t)ops_per_worker;
+  hipError_t e;
+  if ((e = hipMalloc(&P.ch_cnt, cb)) != hipSuccess || (e = hipMalloc(&P.ch_ops, ob)) != hipSuccess ||
+      (e = hipMemsetAsync(P.ch_cnt, 0, cb, h->stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(h->stream)) != hipSuccess) {
+    if (P.ch_cnt) (void)hipFree(P.ch_cnt);
+    if (P.ch_ops) (void)hipFree(P.ch_ops);
+    return fail(PAXISIM_ENOMEM, "client history buffers (%zu bytes): %s", cb + ob, hipGetErrorString(e));
+  }
+  h->P = P;
+  h->ch_bytes = cb + ob;
+  return 0;
+}
+
+// The ops of one cluster, 5 words per op {key, is_write, value, start, end}, workers in index
+// order, each in completion order; *dropped_out: the ops past ops_per_worker, counted only.
+extern "C" int paxisim_client_history(paxisim* h, uint64_t cluster, uint32_t* buf, uint32_t cap_ops, uint32_t* n_out,
+                                      uint32_t* dropped_out) {
+  if (!h || !n_out) return fail(PAXISIM_EINVAL, "null argument");
+  if (!h->P.ch_cap) return fail(PAXISIM_EINVAL, "the client history is not enabled");
+  if (cluster >= h->cfg.clusters) return fail(PAXISIM_ERANGE, "cluster");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
+  const Params& P = h->P;
+  const uint32_t tot = P.WK * P.ch_cap;
+  uint4* d_ops = nullptr;
+  uint32_t* d_cnt = nullptr;
+  std::vector<uint4> tmp(tot);
+  std::vector<uint32_t> cnt(P.WK);
+  hipError_t e = hipMalloc(&d_ops, tot * sizeof(uint4));
+  if (e == hipSuccess) e = hipMalloc(&d_cnt, P.WK * sizeof(uint32_t));
+  if (e == hipSuccess) {
+    chist_read_kernel<<<(tot + 255u) / 256u, 256, 0, h->stream>>>(P, cluster, d_ops, d_cnt);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(tmp.data(), d_ops, tot * sizeof(uint4), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, P.WK * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  (void)hipFree(d_ops);
+  (void)hipFree(d_cnt);
+  if (e != hipSuccess) return fail(PAXISIM_EDEVICE, "client history: %s", hipGetErrorString(e));
+  uint32_t n = 0, dropped = 0;
+  for (uint32_t w = 0; w < P.WK; w++) {
+    const uint32_t len = std::min(cnt[w], P.ch_cap);
+    dropped += cnt[w] - len;
+    for (uint32_t j = 0; j < len; j++, n++) {
+      if (!buf || n >= cap_ops) continue;
+      const uint4& r = tmp[(size_t)w * P.ch_cap + j];
+      uint32_t* o = buf + 5 * (size_t)n;
+      o[0] = r.x & 0x7FFFFFFFu;
+      o[1] = r.x >> 31;
+      o[2] = r.y;
+      o[3] = r.z;
+      o[4] = r.w;
+    }
+  }
+  *n_out = n;
+  if (dropped_out) *dropped_out = dropped;
+  return 0;
+}
+
+// History.ReadFile (history.go:115-178) into the device history of one worker: literal records.
+extern "C" int paxisim_client_history_load(paxisim* h, uint64_t cluster, uint32_t worker, const uint32_t* ops,
+                                           uint32_t n) {
+  if (!h || (n && !ops)) return fail(PAXISIM_EINVAL, "null argument");
+  if (!h->P.ch_cap) return fail(PAXISIM_EINVAL, "the client history is not enabled");
+  if (cluster >= h->cfg.clusters || worker >= h->P.WK) return fail(PAXISIM_ERANGE, "bad worker");
+  if (n > h->P.ch_cap) return fail(PAXISIM_EINVAL, "%u ops exceed history capacity %u", n, h->P.ch_cap);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int rc = pipe_check(h)) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const Params& P = h->P;
+  std::vector<uint4> tmp(n ? n : 1);
+  for (uint32_t j = 0; j < n; j++) {
+    const uint32_t* o = ops + 5 * (size_t)j;
+    if (o[0] >= P.keys || o[1] > 1u) return fail(PAXISIM_EINVAL, "op %u: bad key (keys = %u) or is_write", j, P.keys);
+    tmp[j] = make_uint4(CH_LITERAL | (o[1] ? CH_WRITE : 0u) | o[0], o[2], o[3], o[4]);
+  }
+  const size_t row = chist_row(P, worker, cluster);
+  if (n) HIPCHK(hipMemcpy(&P.ch_ops[row * P.ch_cap], tmp.data(), n * sizeof(uint4), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(&P.ch_cnt[row], &n, 4, hipMemcpyHostToDevice));
+  return 0;
+}
+
+extern "C" int paxisim_client_linearizable(paxisim* h, uint64_t* anomalies, uint64_t* ops, uint64_t* skipped) {
+  if (!h) return fail(PAXISIM_EINVAL, "null handle");
+  if (!h->P.ch_cap) return fail(PAXISIM_EINVAL, "the client history is not enabled");
+  return lin_scan<LinClient>(h, anomalies, ops, skipped);
 }
 
 // ---------------------------------------------------------------------------

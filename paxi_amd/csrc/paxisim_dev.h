@@ -236,6 +236,11 @@ struct Params {
   uint32_t lat_bins;             // one-step histogram bins per worker
   uint32_t* lat_stamp;           // [WK][C] issue step of each worker's request in flight
   unsigned long long* lat_acc;   // [LAT_SLICES][WK][lat_bins + LAT_EXTRA] accumulators
+  // client-side op history (chist_kernel.h); off while ch_cap == 0.  The cluster
+  // index is the local cluster id (not the slot: compaction leaves the rows in place)
+  uint32_t ch_cap;               // ops kept per worker
+  uint4* ch_ops;                 // [WK][C][ch_cap] {cid, reply value, start, end}
+  uint32_t* ch_cnt;              // [WK][C] replies accepted (counts on past ch_cap)
 };
 
 // Persistent scalars of the kpaxos instance (blk, k, r, lane) in the record

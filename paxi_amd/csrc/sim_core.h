@@ -13,6 +13,7 @@
 #pragma once
 #include "paxisim_dev.h"
 #include "lat_kernel.h"
+#include "chist_kernel.h"
 
 namespace pxs {
 
@@ -451,6 +452,9 @@ __device__ __forceinline__ void client_reply(const Params& P, Rep<NT>& x, uint32
   if (x.l_wcur[wi] != cid) return;              // duplicate reply: the worker moved on
   x.replies++;
   if (PXS_LAT) lat_sample(P, x.blk, x.lane, w, x.c, x.t);   // the recording units only (lat_kernel.h)
+  if (PXS_LAT) {
+    if (P.ch_cap) chist_record(P, w, x.gid - P.cluster_base, x.c, cid, value, x.t);   // the op (chist_kernel.h)
+  }
   if (PXS_REPLY_STORE && PXS_REPLY_DEFER) {
     reply_flush<NT>(P, x);
     x.rw = w + 1u;

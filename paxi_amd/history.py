@@ -1,10 +1,11 @@
-"""Client operation history (history.go, operation.go) of simulated ABD runs.
+"""Client operation history (history.go, operation.go) of simulated runs.
 
 `History` mirrors the reference type: operations sharded by key
 (`Add`/`AddOperation`, history.go:31-52), `WriteFile` (history.go:74-113, the
 "history.csv" the benchmark writes at benchmark.go:187) and `ReadFile`
 (history.go:116-178, the 5-column log that checker/checker.go reads).  It is
-filled from the device's recorded ops (`paxisim_history`): a write has
+filled from the device's recorded ops (`paxisim_history`: ABD's replica-side
+history; `paxisim_client_history`: the clients' ops of any protocol): a write has
 input = value and output = nil, a read input = nil and output = value, as the
 benchmark worker records them (benchmark.go:253-273).
 
@@ -58,6 +59,27 @@ class History:
         for c in clusters:
             h = cls()
             for key, is_write, value, start, end in sim.history(c):
+                if is_write:
+                    h.add(key, value, None, start * step_ns, end * step_ns)
+                else:
+                    h.add(key, None, value, start * step_ns, end * step_ns)
+            out.append(h)
+        return out
+
+    @classmethod
+    def from_client(cls, sim, clusters=None, step_ns=1_000_000):
+        """Histories of `clusters` (default: all) of a Simulation of any protocol
+        that records its clients' ops (`Simulation.client_history_enable`,
+        DESIGN.md §3.13), one History per cluster in canonical order: what the
+        benchmark's workers add (benchmark.go:253-273).  Ops dropped past
+        ops_per_worker are not in it."""
+        if clusters is None:
+            clusters = range(sim.cfg.clusters)
+        out = []
+        for c in clusters:
+            h = cls()
+            ops, _ = sim.client_history(c)
+            for key, is_write, value, start, end in ops:
                 if is_write:
                     h.add(key, value, None, start * step_ns, end * step_ns)
                 else:

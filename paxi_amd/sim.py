@@ -93,6 +93,17 @@ def load_library():
         L.paxisim_latency_get.argtypes = [C.c_void_p, C.c_uint32, P(abi.Latency), P(C.c_uint64)]
         L.paxisim_latency_stat_of.restype = C.c_int
         L.paxisim_latency_stat_of.argtypes = [P(abi.Latency), P(C.c_uint64), C.c_double, P(abi.LatencyStat)]
+    # the client-side op history of every protocol: bound where the library has it
+    if hasattr(L, "paxisim_client_history_enable"):
+        L.paxisim_client_history_enable.restype = C.c_int
+        L.paxisim_client_history_enable.argtypes = [C.c_void_p, C.c_uint32]
+        L.paxisim_client_history.restype = C.c_int
+        L.paxisim_client_history.argtypes = [C.c_void_p, C.c_uint64, P(C.c_uint32), C.c_uint32, P(C.c_uint32),
+                                             P(C.c_uint32)]
+        L.paxisim_client_history_load.restype = C.c_int
+        L.paxisim_client_history_load.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, P(C.c_uint32), C.c_uint32]
+        L.paxisim_client_linearizable.restype = C.c_int
+        L.paxisim_client_linearizable.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64), P(C.c_uint64)]
     if L.paxisim_abi_version() != abi.ABI_VERSION:
         raise PaxisimError("ABI version mismatch between paxi_amd/abi.py and libpaxisim.so")
     _lib = L
@@ -111,7 +122,9 @@ EXPORTED = ["paxisim_abi_version", "paxisim_build_id", "paxisim_last_error", "pa
             "paxisim_history_load", "paxisim_active_clusters", "paxisim_read_activity", "paxisim_read_client", "paxisim_quorum", "paxisim_dist_init", "paxisim_dist_unique_id",
             "paxisim_dist_init_rank", "paxisim_dist_allreduce", "paxisim_dist_stats", "paxisim_dist_destroy",
             "paxisim_read_kv", "paxisim_read_inbox", "paxisim_deliver", "paxisim_commands",
-            "paxisim_latency_enable", "paxisim_latency_reset", "paxisim_latency_get", "paxisim_latency_stat_of"]
+            "paxisim_latency_enable", "paxisim_latency_reset", "paxisim_latency_get", "paxisim_latency_stat_of",
+            "paxisim_client_history_enable", "paxisim_client_history", "paxisim_client_history_load",
+            "paxisim_client_linearizable"]
 
 
 def _check(rc):
@@ -296,6 +309,42 @@ class Simulation:
         hist = (C.c_uint64 * abi.LAT_MAX_BINS)()
         _check(fn(self.h, w, C.byref(lat), hist))
         return Histogram(hist[:lat.bins], lat.count, lat.sum, lat.overflow, lat.min, lat.max)
+
+    # client-side op history of every protocol (benchmark.go:246-275, history.go)
+    @staticmethod
+    def _chist(name):
+        fn = getattr(load_library(), name, None)
+        if fn is None:
+            raise PaxisimError(f"{LIB_PATH} was built without {name} (client-side op history)")
+        return fn
+
+    def client_history_enable(self, ops_per_worker):
+        """Record every worker's completed ops, `ops_per_worker` per worker and cluster (later ones
+        are counted as dropped); once, before the first step and after latency_enable."""
+        _check(self._chist("paxisim_client_history_enable")(self.h, ops_per_worker))
+
+    def client_history(self, cluster):
+        """([(key, is_write, value, start, end)] in canonical order - worker 0's ops in completion
+        order, then worker 1's, ... -, ops dropped past ops_per_worker) of one cluster."""
+        fn = self._chist("paxisim_client_history")
+        n, d = C.c_uint32(), C.c_uint32()
+        _check(fn(self.h, cluster, None, 0, C.byref(n), C.byref(d)))
+        buf = (C.c_uint32 * max(1, 5 * n.value))()
+        _check(fn(self.h, cluster, buf, n.value, C.byref(n), C.byref(d)))
+        return [tuple(buf[5 * i: 5 * i + 5]) for i in range(n.value)], d.value
+
+    def client_history_load(self, cluster, worker, ops):
+        """History.ReadFile into the device (paxisim_client_history_load): replace one worker's
+        ops with (key, is_write, value, start, end) tuples."""
+        flat = [int(v) for o in ops for v in o]
+        buf = (C.c_uint32 * max(1, len(flat)))(*flat)
+        _check(self._chist("paxisim_client_history_load")(self.h, cluster, worker, buf, len(ops)))
+
+    def client_linearizable(self):
+        """History.Linearizable over the client histories: (anomalies, ops checked, partitions skipped)."""
+        a, n, sk = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(self._chist("paxisim_client_linearizable")(self.h, C.byref(a), C.byref(n), C.byref(sk)))
+        return a.value, n.value, sk.value
 
     def close(self):
         if self.h:

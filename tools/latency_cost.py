@@ -5,12 +5,15 @@ Drop/Slow faults, 1M clusters) with latency off and on in mirrored order (off,
 on, on, off), each a fresh handle, and times the step launches with
 paxisim_kernel_time (HIP events on the launch stream).  Prints one JSON line:
 ms per bench step of each run, the on-cost, the histogram's Stat and the
-library's build id.
-usage: python tools/latency_cost.py [--clusters N] [--steps K] [--warmup W] [--bins B]"""
+library's build id.  With --history N the "on" runs also record the client-side
+op history, N ops per worker, and report the time of
+paxisim_client_linearizable over the handle (host wall clock around the call).
+usage: python tools/latency_cost.py [--clusters N] [--steps K] [--warmup W] [--bins B] [--history N]"""
 import argparse
 import json
 import os
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -24,6 +27,8 @@ def run(args, on):
     with sim.Simulation(cfg, wl, fp, faults) as g:
         if on:
             g.latency_enable(args.bins)
+            if args.history:
+                g.client_history_enable(args.history)
         for _ in range(args.warmup):
             g.step(args.sim_steps)
         g.sync()
@@ -43,6 +48,12 @@ def run(args, on):
             assert h.count == after.replies - before.replies, (h.count, after.replies - before.replies)
             out["stat_steps"] = h.stat(1.0).as_dict()
             out["overflow"] = h.overflow
+        if on and args.history:
+            t0 = time.perf_counter()
+            anomalies, ops, skipped = g.client_linearizable()
+            out["scan_s"] = time.perf_counter() - t0
+            out["scan"] = {"anomalies": anomalies, "ops": ops, "skipped": skipped}
+            out["device_bytes"] = g.device_bytes()
         return out
 
 
@@ -54,13 +65,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--bins", type=int, default=256)
+    ap.add_argument("--history", type=int, default=0, help="also record the client op history, N ops per worker")
     args = ap.parse_args()
     args.window, args.mbox, args.kv = d["window"], d["mbox"], 1
     runs = [run(args, on) for on in (False, True, True, False)]
     off = [r["kernel_ms_per_step"] for r in runs if not r["latency"]]
     on = [r["kernel_ms_per_step"] for r in runs if r["latency"]]
     print(json.dumps({"build_id": sim.build_id(), "clusters": args.clusters, "sim_steps": args.sim_steps,
-                      "steps": args.steps, "warmup": args.warmup, "bins": args.bins, "runs": runs,
+                      "steps": args.steps, "warmup": args.warmup, "bins": args.bins, "history": args.history, "runs": runs,
                       "off_ms": off, "on_ms": on,
                       "on_cost_percent": 100.0 * (sum(on) / sum(off) - 1.0)}))
 
