@@ -553,6 +553,43 @@ int  paxisim_client_history_load(paxisim* h, uint64_t cluster, uint32_t worker, 
  * anomalous reads, ops checked, partitions skipped (paxisim_linearizable). */
 int  paxisim_client_linearizable(paxisim* h, uint64_t* anomalies, uint64_t* ops, uint64_t* skipped);
 
+/* ---- Multi-version Database and Consensus (config.MultiVersion: db.go:123-155
+ * put / History, http.go:121-135 /history, client.go:279-320 Consensus;
+ * DESIGN.md §3.14).  Every value a replica's Database puts to a key is appended
+ * to that key's history at that replica; a write's value is its command id, as
+ * in paxisim_read_kv.  A replica's History(k) is therefore its execution log
+ * filtered to the writes of key k, repeated where EPaxos executes a command
+ * again.  The device keeps the count n of values ever put and the first
+ * versions_per_key of them per (local cluster, replica, key); later puts are
+ * counted, not kept, and raise no flag.  Consensus(k) of a cluster holds when,
+ * index by index, the values present in the replicas' histories of k form a
+ * set of at most one; it is evaluated over the kept prefixes, so with
+ * dropped == 0 it is exactly the reference's predicate. */
+#define PAXISIM_MV_MAX (1u << 16)
+/* Start recording.  Once, before the first step and after
+ * paxisim_latency_enable, whose step kernels it uses (EINVAL otherwise, and for
+ * versions_per_key outside [1, PAXISIM_MV_MAX]).  EUNSUPP with config.kv == 0
+ * (the replicas keep no Database) and for ABD: ABD's KV is written by versioned
+ * Sets, not by Execute of a log, so there is no put order to record.  ENOMEM:
+ * the buffers take keys x replicas x clusters (rounded up to 64) x
+ * (versions_per_key + 1) x 4 bytes. */
+int  paxisim_multiversion_enable(paxisim* h, uint32_t versions_per_key);
+/* Database.History(key) of one replica of a local cluster: *n_out is the number
+ * of values kept, min(n, versions_per_key), of which at most cap are written to
+ * values (may be NULL); *dropped_out (may be NULL) is n - kept.  ERANGE for a
+ * cluster outside the handle, EINVAL for a replica or key that does not exist
+ * or when multiversion is not enabled. */
+int  paxisim_kv_history(paxisim* h, uint64_t cluster, uint32_t replica, uint32_t key,
+                        uint32_t* values, uint32_t cap, uint32_t* n_out, uint32_t* dropped_out);
+/* Consensus over every (cluster, key) of the handle (any pointer may be NULL):
+ * failed, the pairs for which Consensus(k) is false over the kept prefixes;
+ * versions, the sum of n (equal to the sum of paxisim_replica_state.
+ * executed_writes); dropped, the sum of n - kept. */
+int  paxisim_consensus(paxisim* h, uint64_t* failed, uint64_t* versions, uint64_t* dropped);
+/* Per local cluster of [cluster_lo, cluster_lo + n): bit k of key_masks[i] is
+ * set when Consensus(k) is false in cluster cluster_lo + i. */
+int  paxisim_consensus_failed(paxisim* h, uint64_t cluster_lo, uint64_t n, uint64_t* key_masks);
+
 /* ---- Multi-GPU: clusters shard by range over handles
  * (paxisim_config.cluster_base = rank * clusters), the simulation itself has
  * no collective, and totals are reduced with RCCL (opened at run time:

@@ -19,6 +19,7 @@ CLIENT_SRC = 31
 ALL_DST = 0xFF
 LAT_MAX_BINS = 4096          # paxisim_latency_enable: bins is a power of two in [16, LAT_MAX_BINS]
 ALL_WORKERS = 0xFFFFFFFF     # paxisim_latency_get: every worker summed
+MV_MAX = 1 << 16             # paxisim_multiversion_enable: versions_per_key is in [1, MV_MAX]
 
 # error codes
 OK, EINVAL, ENOMEM, EDEVICE, EUNSUPP, ERANGE = 0, -1, -2, -3, -4, -5
@@ -225,6 +226,17 @@ class Stats(C.Structure):
         d["delivered"] = {MSG_NAMES.get(i, str(i)): self.delivered[i] for i in range(NMSG) if self.delivered[i]}
         d["flagged"] = list(self.flagged)
         return d
+
+
+# C prototypes of the multi-version Database calls, every one returning int:
+# the product library only, bound where a library has them (paxi_amd.sim.load_library).
+MV_PROTOTYPES = {
+    "paxisim_multiversion_enable": [C.c_void_p, C.c_uint32],
+    "paxisim_kv_history": [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32,
+                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "paxisim_consensus": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "paxisim_consensus_failed": [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)],
+}
 
 
 # C prototypes shared by the product library (prefix "paxisim") and the oracle ("oracle").

@@ -19,6 +19,7 @@
 
 #define PXS_LAT_REDUCE   // this unit defines and launches lat_reduce (lat_kernel.h)
 #define PXS_CHIST_READ   // and chist_read_kernel (chist_kernel.h)
+#define PXS_MV_SCAN      // and mv_consensus_kernel (mv_kernel.h)
 #include "epaxos_kernel.h"
 #include "lin_kernel.h"
 #include "paxisim_dev.h"
@@ -78,6 +79,7 @@ struct paxisim {
   unsigned long long* d_lat_out = nullptr;
   size_t lat_bytes = 0;
   size_t ch_bytes = 0;             // client-side op history (chist_kernel.h): P.ch_ops and P.ch_cnt
+  size_t mv_bytes = 0;             // multi-version Database (mv_kernel.h): P.mv_val and P.mv_cnt
 };
 
 static inline size_t rc_host(const Params& P, uint32_t r, uint64_t c) { return (size_t)r * P.C + c; }
@@ -940,6 +942,8 @@ extern "C" int paxisim_destroy(paxisim* h) {
   if (h->d_lat_out) (void)hipFree(h->d_lat_out);
   if (h->P.ch_ops) (void)hipFree(h->P.ch_ops);
   if (h->P.ch_cnt) (void)hipFree(h->P.ch_cnt);
+  if (h->P.mv_val) (void)hipFree(h->P.mv_val);
+  if (h->P.mv_cnt) (void)hipFree(h->P.mv_cnt);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return 0;
@@ -1860,7 +1864,7 @@ extern "C" int paxisim_occupancy(paxisim* h, int* blocks_per_cu, uint32_t* lds_b
 
 extern "C" int paxisim_device_bytes(paxisim* h, uint64_t* bytes) {
   if (!h || !bytes) return fail(PAXISIM_EINVAL, "null argument");
-  *bytes = h->arena_bytes + h->lat_bytes + h->ch_bytes;
+  *bytes = h->arena_bytes + h->lat_bytes + h->ch_bytes + h->mv_bytes;
   return 0;
 }
 
@@ -2232,6 +2236,118 @@ extern "C" int paxisim_client_linearizable(paxisim* h, uint64_t* anomalies, uint
   if (!h) return fail(PAXISIM_EINVAL, "null handle");
   if (!h->P.ch_cap) return fail(PAXISIM_EINVAL, "the client history is not enabled");
   return lin_scan<LinClient>(h, anomalies, ops, skipped);
+}
+
+// ---------------------------------------------------------------------------
+// Multi-version Database and Consensus (include/paxisim.h, DESIGN.md §3.14, mv_kernel.h)
+// ---------------------------------------------------------------------------
+extern "C" int paxisim_multiversion_enable(paxisim* h, uint32_t versions_per_key) {
+  if (!h) return fail(PAXISIM_EINVAL, "null handle");
+  if (versions_per_key == 0 || versions_per_key > PAXISIM_MV_MAX)
+    return fail(PAXISIM_EINVAL, "versions_per_key must be in [1, %u]", PAXISIM_MV_MAX);
+  if (h->P.mv_cap) return fail(PAXISIM_EINVAL, "multiversion is already enabled");
+  if (h->t) return fail(PAXISIM_EINVAL, "multiversion can only be enabled before the first step");
+  if (!h->P.lat_bins)
+    return fail(PAXISIM_EINVAL, "multiversion needs the recording step kernels: call paxisim_latency_enable first");
+  if (h->P.protocol == PAXISIM_ABD)
+    return fail(PAXISIM_EUNSUPP, "ABD's KV is written by versioned Sets, not by Execute of a log: no put order to record");
+  if (!h->P.kv) return fail(PAXISIM_EUNSUPP, "replicas keep no Database (config.kv = 0)");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  Params P = h->P;
+  P.mv_cap = versions_per_key;
+  const size_t rows = (size_t)P.keys * P.N * P.C;
+  const size_t cb = sizeof(uint32_t) * rows, vb = cb * versions_per_key;
+  hipError_t e;
+  if ((e = hipMalloc(&P.mv_cnt, cb)) != hipSuccess || (e = hipMalloc(&P.mv_val, vb)) != hipSuccess ||
+      (e = hipMemsetAsync(P.mv_cnt, 0, cb, h->stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(h->stream)) != hipSuccess) {
+    if (P.mv_cnt) (void)hipFree(P.mv_cnt);
+    if (P.mv_val) (void)hipFree(P.mv_val);
+    return fail(PAXISIM_ENOMEM, "multiversion buffers (%zu bytes): %s", cb + vb, hipGetErrorString(e));
+  }
+  h->P = P;
+  h->mv_bytes = cb + vb;
+  return 0;
+}
+
+// Database.History(key) of one replica: the row is contiguous and indexed by the cluster id, so
+// the readout is a copy of the count and one of the kept values.
+extern "C" int paxisim_kv_history(paxisim* h, uint64_t cluster, uint32_t replica, uint32_t key, uint32_t* values,
+                                  uint32_t cap, uint32_t* n_out, uint32_t* dropped_out) {
+  if (!h || !n_out) return fail(PAXISIM_EINVAL, "null argument");
+  if (!h->P.mv_cap) return fail(PAXISIM_EINVAL, "multiversion is not enabled");
+  if (cluster >= h->cfg.clusters) return fail(PAXISIM_ERANGE, "cluster");
+  if (replica >= h->P.N || key >= h->P.keys) return fail(PAXISIM_EINVAL, "no replica %u or key %u", replica, key);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
+  const Params& P = h->P;
+  const size_t row = mv_row(P, key, replica, cluster);
+  uint32_t n = 0;
+  HIPCHK(hipMemcpyAsync(&n, &P.mv_cnt[row], sizeof n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const uint32_t kept = std::min(n, P.mv_cap), take = values ? std::min(kept, cap) : 0u;
+  if (take) {
+    HIPCHK(hipMemcpyAsync(values, &P.mv_val[row * P.mv_cap], take * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  *n_out = kept;
+  if (dropped_out) *dropped_out = n - kept;
+  return 0;
+}
+
+// client.go:279-320 over clusters [lo, lo + n): totals into tot[MV_NOUT], the failing keys of each
+// cluster into masks (either may be null).
+static int mv_scan(paxisim* h, uint64_t lo, uint64_t n, uint64_t* tot, uint64_t* masks) {
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
+  const Params& P = h->P;
+  unsigned long long* d_masks = nullptr;
+  if (masks) {
+    HIPCHK(hipMalloc(&d_masks, n * sizeof(unsigned long long)));
+    hipError_t e = hipMemsetAsync(d_masks, 0, n * sizeof(unsigned long long), h->stream);
+    if (e != hipSuccess) {
+      (void)hipFree(d_masks);
+      return fail(PAXISIM_EDEVICE, "consensus: %s", hipGetErrorString(e));
+    }
+  }
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(h->d_scratch);
+  uint64_t res[MV_NOUT] = {0, 0, 0};
+  // a wave per (cluster, key), dealt grid-stride: enough workgroups to fill the device, no more
+  const uint64_t pairs = n * P.keys;
+  const unsigned grid = (unsigned)std::min<uint64_t>((pairs + MV_WAVES - 1) / MV_WAVES, 8192);
+  hipError_t e = hipMemsetAsync(out, 0, sizeof res, h->stream);
+  if (e == hipSuccess) {
+    mv_consensus_kernel<<<grid, MV_WAVES * 64, 0, h->stream>>>(P, lo, n, out, d_masks);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(res, out, sizeof res, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess && masks)
+    e = hipMemcpyAsync(masks, d_masks, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (d_masks) (void)hipFree(d_masks);
+  if (e != hipSuccess) return fail(PAXISIM_EDEVICE, "consensus: %s", hipGetErrorString(e));
+  if (tot)
+    for (int i = 0; i < MV_NOUT; i++) tot[i] = res[i];
+  return 0;
+}
+
+extern "C" int paxisim_consensus(paxisim* h, uint64_t* failed, uint64_t* versions, uint64_t* dropped) {
+  if (!h) return fail(PAXISIM_EINVAL, "null handle");
+  if (!h->P.mv_cap) return fail(PAXISIM_EINVAL, "multiversion is not enabled");
+  uint64_t tot[MV_NOUT];
+  if (const int rc = mv_scan(h, 0, h->cfg.clusters, tot, nullptr)) return rc;
+  if (failed) *failed = tot[MV_FAILED];
+  if (versions) *versions = tot[MV_VERSIONS];
+  if (dropped) *dropped = tot[MV_DROPPED];
+  return 0;
+}
+
+extern "C" int paxisim_consensus_failed(paxisim* h, uint64_t cluster_lo, uint64_t n, uint64_t* key_masks) {
+  if (!h || (n && !key_masks)) return fail(PAXISIM_EINVAL, "null argument");
+  if (!h->P.mv_cap) return fail(PAXISIM_EINVAL, "multiversion is not enabled");
+  if (cluster_lo > h->cfg.clusters || n > h->cfg.clusters - cluster_lo) return fail(PAXISIM_ERANGE, "cluster range");
+  if (n == 0) return 0;
+  return mv_scan(h, cluster_lo, n, nullptr, key_masks);
 }
 
 // ---------------------------------------------------------------------------

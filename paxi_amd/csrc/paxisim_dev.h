@@ -241,6 +241,11 @@ struct Params {
   uint32_t ch_cap;               // ops kept per worker
   uint4* ch_ops;                 // [WK][C][ch_cap] {cid, reply value, start, end}
   uint32_t* ch_cnt;              // [WK][C] replies accepted (counts on past ch_cap)
+  // multi-version Database (mv_kernel.h); off while mv_cap == 0.  The cluster index
+  // is the local cluster id, as for the client history
+  uint32_t mv_cap;               // values kept per (key, replica, cluster)
+  uint32_t* mv_val;              // [K][N][C][mv_cap] the first mv_cap values put (command ids)
+  uint32_t* mv_cnt;              // [K][N][C] values ever put (counts on past mv_cap)
 };
 
 // Persistent scalars of the kpaxos instance (blk, k, r, lane) in the record

@@ -500,6 +500,9 @@ __device__ __forceinline__ void kv_exec(const Params& P, Rep<NT>& x, uint32_t h,
   PXS_TALLY_AT(P, x.blk, TC_KV_ST, &P.kv_val[((size_t)key * nrep<NT>(P) + x.r) * P.C + x.c], true);
   P.kv_val[((size_t)key * nrep<NT>(P) + x.r) * P.C + x.c] = cmd;
   x.kvver++;
+  if (PXS_LAT) {
+    if (P.mv_cap) mv_put(P, key, x.r, x.gid - P.cluster_base, cmd);   // history[key] (mv_kernel.h)
+  }
 }
 
 // hi / hc: the entry index and flags the caller has just written, which exec

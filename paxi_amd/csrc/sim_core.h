@@ -14,6 +14,7 @@
 #include "paxisim_dev.h"
 #include "lat_kernel.h"
 #include "chist_kernel.h"
+#include "mv_kernel.h"
 
 namespace pxs {
 

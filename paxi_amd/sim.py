@@ -104,6 +104,12 @@ def load_library():
         L.paxisim_client_history_load.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, P(C.c_uint32), C.c_uint32]
         L.paxisim_client_linearizable.restype = C.c_int
         L.paxisim_client_linearizable.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64), P(C.c_uint64)]
+    # the multi-version Database and Consensus: likewise
+    if hasattr(L, "paxisim_multiversion_enable"):
+        for name, args in abi.MV_PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.restype = C.c_int
+            fn.argtypes = args
     if L.paxisim_abi_version() != abi.ABI_VERSION:
         raise PaxisimError("ABI version mismatch between paxi_amd/abi.py and libpaxisim.so")
     _lib = L
@@ -124,7 +130,22 @@ EXPORTED = ["paxisim_abi_version", "paxisim_build_id", "paxisim_last_error", "pa
             "paxisim_read_kv", "paxisim_read_inbox", "paxisim_deliver", "paxisim_commands",
             "paxisim_latency_enable", "paxisim_latency_reset", "paxisim_latency_get", "paxisim_latency_stat_of",
             "paxisim_client_history_enable", "paxisim_client_history", "paxisim_client_history_load",
-            "paxisim_client_linearizable"]
+            "paxisim_client_linearizable",
+            "paxisim_multiversion_enable", "paxisim_kv_history", "paxisim_consensus", "paxisim_consensus_failed"]
+
+
+def consensus_of_histories(histories):
+    """HTTPClient.Consensus (client.go:302-319) over the replicas' History(k) lists: at every index
+    the values present form a set of at most one.  (True, None), or (False, the first index that fails)."""
+    n = max((len(h) for h in histories), default=0)
+    for i in range(n):
+        present = set()
+        for h in histories:
+            if len(h) > i:
+                present.add(h[i])
+        if len(present) > 1:
+            return False, i
+    return True, None
 
 
 def _check(rc):
@@ -345,6 +366,48 @@ class Simulation:
         a, n, sk = C.c_uint64(), C.c_uint64(), C.c_uint64()
         _check(self._chist("paxisim_client_linearizable")(self.h, C.byref(a), C.byref(n), C.byref(sk)))
         return a.value, n.value, sk.value
+
+    # multi-version Database and Consensus (db.go:123-155, client.go:279-320)
+    @staticmethod
+    def _mv(name):
+        fn = getattr(load_library(), name, None)
+        if fn is None:
+            raise PaxisimError(f"{LIB_PATH} was built without {name} (multi-version Database)")
+        return fn
+
+    def multiversion_enable(self, versions_per_key):
+        """Keep every replica's History(key): the first `versions_per_key` values put per key (later
+        ones are counted as dropped); once, before the first step and after latency_enable."""
+        _check(self._mv("paxisim_multiversion_enable")(self.h, versions_per_key))
+        self._mv_cap = versions_per_key
+
+    def kv_history(self, cluster, replica, key):
+        """Database.History(key) of one replica: (the values kept, in put order; values dropped)."""
+        fn = self._mv("paxisim_kv_history")
+        cap = getattr(self, "_mv_cap", 0)
+        buf = (C.c_uint32 * max(1, cap))()
+        n, d = C.c_uint32(), C.c_uint32()
+        _check(fn(self.h, cluster, replica, key, buf, cap, C.byref(n), C.byref(d)))
+        return list(buf[:n.value]), d.value
+
+    def consensus(self):
+        """Consensus over every (cluster, key): (pairs that fail over the kept prefixes, values ever
+        put, values dropped)."""
+        f, v, d = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(self._mv("paxisim_consensus")(self.h, C.byref(f), C.byref(v), C.byref(d)))
+        return f.value, v.value, d.value
+
+    def consensus_failed(self, lo=0, n=None):
+        """Per cluster of [lo, lo + n): the bit mask of the keys whose Consensus fails."""
+        n = self.cfg.clusters - lo if n is None else n
+        buf = (C.c_uint64 * max(1, n))()
+        _check(self._mv("paxisim_consensus_failed")(self.h, lo, n, buf))
+        return list(buf[:n])
+
+    def consensus_of(self, cluster, key):
+        """HTTPClient.Consensus(key) of one cluster from the replicas' readouts: (True, None), or
+        (False, the first index at which two replicas hold different values)."""
+        return consensus_of_histories([self.kv_history(cluster, r, key)[0] for r in range(self.N)])
 
     def close(self):
         if self.h:
