@@ -24,6 +24,7 @@
 #include "lin_kernel.h"
 #include "paxisim_dev.h"
 #include "sim_core.h"
+#include "pool_plan.h"
 #include "step_ops.h"
 
 using namespace pxs;
@@ -43,6 +44,19 @@ static int fail(int code, const char* fmt, ...) {
       return fail(PAXISIM_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));    \
   } while (0)
 
+// A cluster pool: a slot region that is stepped, compacted and phase-binned on
+// its own stream.  Swaps never cross regions; slot_of / cl_of and every array stay global.
+struct Pool {
+  uint32_t base = 0, end = 0;      // slots [base, end); base a multiple of 512
+  uint32_t* d_cmp = nullptr;       // [0] bound (absolute), [1] lnew, [2] npairs, [3] live, [4] live before lnew, then block sums
+  uint32_t* d_pairs = nullptr;     // [2][C/2+64]: dead slots below lnew, live slots above it
+  uint32_t* d_ph = nullptr;        // phase binning: class counts, region, per-block sums
+  uint32_t* d_pipe = nullptr;      // [0,8) tickets, [8] error, [16, 16 + max(C/64, 64)) chunks done per tile
+  hipStream_t stream = nullptr;    // one pool: the handle's stream
+  hipEvent_t ev = nullptr;         // join: the pool's work so far (two pools only)
+  uint32_t last_cmp = 0;
+};
+
 struct paxisim {
   paxisim_config cfg;
   paxisim_workload wl;
@@ -52,7 +66,6 @@ struct paxisim {
   std::vector<DevFault> faults;
   DevFault* d_faults = nullptr;
   uint32_t* d_move = nullptr;      // moving-Mu key CDF tables (paxisim_workload.move_cdf)
-  uint32_t* d_ph = nullptr;        // phase binning: class counts, region, per-block sums
   void* arena = nullptr;
   size_t arena_bytes = 0;
   uint64_t* d_scratch = nullptr;   // reductions
@@ -64,14 +77,18 @@ struct paxisim {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
   double kernel_ms = 0;
   uint64_t launches = 0;
-  // live-cluster compaction
-  uint32_t* d_cmp = nullptr;       // [0] bound, [1] lnew, [2] npairs, [3] live, [4] live before lnew, then block sums
-  uint32_t* d_pairs = nullptr;     // [2][C/2+64]: dead slots below lnew, live slots above it
+  // live-cluster compaction: per pool, the scratch in Pool
   uint32_t cmp_every = 50;         // steps between compactions
   // pipelined serial launches (sim_core.h sim_serial_pipe): up to pipe_max chunks of S steps per launch
   uint32_t pipe_max = 4;
-  uint32_t* d_pipe = nullptr;      // [0,8) tickets, [8] error, [16, 16 + max(C/64, 64)) chunks done per tile
-  uint32_t last_cmp = 0;
+  uint32_t pipe_slots = 0;         // PAXISIM_PIPE_SLOTS: cap on the persistent grid (0: none)
+  // cluster pools: pool[0] alone steps on `stream`; two pools step on streams of their own, and
+  // everything that is not a step stays on `stream` behind a join (join_pools)
+  Pool pool[MAX_POOLS];
+  uint32_t npools = 1;
+  hipEvent_t ev_main = nullptr;    // join: the handle's stream so far
+  bool pools_ahead = false;        // steps were launched since the last join
+  bool main_ahead = false;         // the handle's stream was used since the last step
   uint32_t late_until = 0;         // no compaction before every late worker has started
   uint32_t bound_host = 0;         // last bound read back (diagnostics)
   uint64_t lin_big = 0, lin_nmax = 0;   // last linearizability scan: partitions above LIN_SMAX, largest
@@ -592,8 +609,10 @@ __device__ void swap_slots(const Params& P, uint64_t p, uint64_t q, uint32_t j) 
   }
 }
 
-__global__ void cmp_count(Params P, uint32_t* cm) {
-  const uint64_t s = (uint64_t)blockIdx.x * CB + threadIdx.x;
+// The compaction and phase-binning kernels work on one pool's region: slot s = base + ..., the
+// bound in cm[CM_BOUND] absolute and never past the region's end.
+__global__ void cmp_count(Params P, uint32_t* cm, uint32_t base) {
+  const uint64_t s = base + (uint64_t)blockIdx.x * CB + threadIdx.x;
   const int live = s < cm[CM_BOUND] && !P.qf[s];
   const int n = __syncthreads_count(live);
   if (threadIdx.x == 0) cm[CM_SUMS + blockIdx.x] = (uint32_t)n;
@@ -601,7 +620,7 @@ __global__ void cmp_count(Params P, uint32_t* cm) {
 
 // one workgroup of CB threads: exclusive scan of the block counts, then the
 // new bound and the number of pairs to swap
-__global__ void cmp_scan(Params P, uint32_t* cm, uint32_t nb) {
+__global__ void cmp_scan(Params P, uint32_t* cm, uint32_t nb, uint32_t base) {
   __shared__ uint32_t sh[CB];
   __shared__ uint32_t carry;
   const uint32_t tid = threadIdx.x;
@@ -623,10 +642,10 @@ __global__ void cmp_scan(Params P, uint32_t* cm, uint32_t nb) {
     __syncthreads();
   }
   const uint32_t live = carry, bound = cm[CM_BOUND];
-  uint32_t lnew = (live + LANES - 1u) / LANES * LANES;
+  uint32_t lnew = base + (live + LANES - 1u) / LANES * LANES;
   if (lnew > bound) lnew = bound;
-  const uint32_t b = lnew / CB;
-  const uint64_t s = (uint64_t)b * CB + tid;
+  const uint32_t b = (lnew - base) / CB;
+  const uint64_t s = base + (uint64_t)b * CB + tid;
   const int cnt = __syncthreads_count(s < lnew && !P.qf[s]);
   const uint32_t lbl = (b < nb ? cm[CM_SUMS + b] : live) + (uint32_t)cnt;   // live slots below lnew
   if (tid == 0) {
@@ -637,9 +656,9 @@ __global__ void cmp_scan(Params P, uint32_t* cm, uint32_t nb) {
   }
 }
 
-__global__ void cmp_index(Params P, uint32_t* cm, uint32_t* lo, uint32_t* hi) {
+__global__ void cmp_index(Params P, uint32_t* cm, uint32_t* lo, uint32_t* hi, uint32_t base) {
   __shared__ uint32_t wsum[CB / LANES];
-  const uint64_t s = (uint64_t)blockIdx.x * CB + threadIdx.x;
+  const uint64_t s = base + (uint64_t)blockIdx.x * CB + threadIdx.x;
   const uint32_t bound = cm[CM_BOUND], lnew = cm[CM_LNEW], lbl = cm[CM_LBL], np = cm[CM_NPAIRS];
   const bool live = s < bound && !P.qf[s];
   const uint64_t m = __ballot(live);
@@ -649,10 +668,10 @@ __global__ void cmp_index(Params P, uint32_t* cm, uint32_t* lo, uint32_t* hi) {
   __syncthreads();
   uint32_t off = 0;
   for (uint32_t k = 0; k < w; k++) off += wsum[k];
-  const uint32_t before = cm[CM_SUMS + blockIdx.x] + off + inw;     // live slots in [0, s)
+  const uint32_t before = cm[CM_SUMS + blockIdx.x] + off + inw;     // live slots in [base, s)
   if (s >= bound) return;
   if (!live && s < lnew) {
-    const uint32_t k = (uint32_t)s - before;                       // dead slots in [0, s)
+    const uint32_t k = (uint32_t)s - base - before;                // dead slots in [base, s)
     if (k < np) lo[k] = (uint32_t)s;
   } else if (live && s >= lnew) {
     hi[before - lbl] = (uint32_t)s;
@@ -664,8 +683,8 @@ __global__ void cmp_swap(Params P, const uint32_t* cm, const uint32_t* lo, const
   for (uint32_t k = blockIdx.x; k < np; k += gridDim.x) swap_slots(P, lo[k], hi[k], threadIdx.x);
 }
 
-__global__ void cmp_freeze(Params P, uint32_t* cm, uint32_t t) {
-  const uint64_t s = (uint64_t)blockIdx.x * CB + threadIdx.x;
+__global__ void cmp_freeze(Params P, uint32_t* cm, uint32_t t, uint32_t base) {
+  const uint64_t s = base + (uint64_t)blockIdx.x * CB + threadIdx.x;
   if (s >= cm[CM_LNEW] && s < cm[CM_BOUND]) P.frz[s] = t;
 }
 __global__ void cmp_setbound(uint32_t* cm) { cm[CM_BOUND] = cm[CM_LNEW]; }
@@ -685,8 +704,8 @@ enum { PH_N = 0, PH_BASE = 8, PH_END = 9, PH_SUMS = 16 };   // PH_N + class: cla
 __device__ __forceinline__ uint32_t ph_class(const Params& P, uint64_t s) {
   return P.qf[s] ? P.phase_period : P.phase[s];
 }
-__global__ void ph_classes(Params P, const uint32_t* cm, uint32_t* ph) {
-  const uint64_t s = (uint64_t)blockIdx.x * CB + threadIdx.x;
+__global__ void ph_classes(Params P, const uint32_t* cm, uint32_t* ph, uint32_t base) {
+  const uint64_t s = base + (uint64_t)blockIdx.x * CB + threadIdx.x;
   const uint32_t bound = cm[CM_BOUND];
   const uint32_t c = s < bound ? ph_class(P, s) : 0xFFu;
   for (uint32_t k = 0; k <= P.phase_period; k++) {
@@ -695,15 +714,15 @@ __global__ void ph_classes(Params P, const uint32_t* cm, uint32_t* ph) {
   }
 }
 // region of class p: [sum of classes < p, + count of p)
-__global__ void ph_region(uint32_t* ph, uint32_t p) {
-  uint32_t b = 0;
+__global__ void ph_region(uint32_t* ph, uint32_t p, uint32_t base) {
+  uint32_t b = base;
   for (uint32_t k = 0; k < p; k++) b += ph[PH_N + k];
   ph[PH_BASE] = b;
   ph[PH_END] = b + ph[PH_N + p];
 }
 // per block: misplaced slots inside the region (class != p) and class-p slots beyond it
-__global__ void ph_count(Params P, const uint32_t* cm, uint32_t* ph, uint32_t p, uint32_t nb) {
-  const uint64_t s = (uint64_t)blockIdx.x * CB + threadIdx.x;
+__global__ void ph_count(Params P, const uint32_t* cm, uint32_t* ph, uint32_t p, uint32_t nb, uint32_t sbase) {
+  const uint64_t s = sbase + (uint64_t)blockIdx.x * CB + threadIdx.x;
   const uint32_t bound = cm[CM_BOUND], base = ph[PH_BASE], end = ph[PH_END];
   const uint32_t c = s < bound ? ph_class(P, s) : 0xFFu;
   const int in = __syncthreads_count(s >= base && s < end && c != p);
@@ -741,9 +760,9 @@ __global__ void ph_scan(uint32_t* cm, uint32_t* ph, uint32_t nb) {
   }
 }
 __global__ void ph_index(Params P, const uint32_t* cm, const uint32_t* ph, uint32_t p, uint32_t nb, uint32_t* lo,
-                         uint32_t* hi) {
+                         uint32_t* hi, uint32_t sbase) {
   __shared__ uint32_t wa[CB / LANES], wb[CB / LANES];
-  const uint64_t s = (uint64_t)blockIdx.x * CB + threadIdx.x;
+  const uint64_t s = sbase + (uint64_t)blockIdx.x * CB + threadIdx.x;
   const uint32_t bound = cm[CM_BOUND], base = ph[PH_BASE], end = ph[PH_END];
   const uint32_t c = s < bound ? ph_class(P, s) : 0xFFu;
   const bool in = s >= base && s < end && c != p, out = s >= end && s < bound && c == p;
@@ -909,13 +928,53 @@ static T* carve(char*& p, size_t count) {
 }
 
 static int pipe_check(paxisim* h);
+
+// Every entry point but paxisim_step works on the handle's stream.  With two pools it first makes
+// that stream wait for what the pools' streams have been given (an event on each), and notes that
+// the next paxisim_step must make the pools' streams wait for the handle's; consecutive steps with
+// nothing between them add no dependency between streams.
+static int enter(paxisim* h) {
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (h->npools > 1) {
+    if (h->pools_ahead) {
+      for (uint32_t p = 0; p < h->npools; p++) {
+        HIPCHK(hipEventRecord(h->pool[p].ev, h->pool[p].stream));
+        HIPCHK(hipStreamWaitEvent(h->stream, h->pool[p].ev, 0));
+      }
+      h->pools_ahead = false;
+    }
+    h->main_ahead = true;
+  }
+  return 0;
+}
+
+// Kernel time: one pool, the sum of the launches' times; two pools, whose launches overlap, the
+// length of the union of their [start, end] intervals, each taken against the batch's first event.
 static int flush_events(paxisim* h) {
   const bool any = !h->evs.empty();
+  std::vector<std::pair<double, double>> iv;
   for (auto& e : h->evs) {
     float ms = 0;
     HIPCHK(hipEventSynchronize(e.second));
     HIPCHK(hipEventElapsedTime(&ms, e.first, e.second));
-    h->kernel_ms += ms;
+    if (h->npools > 1) {
+      float at = 0;
+      if (e.first != h->evs[0].first) {
+        HIPCHK(hipEventSynchronize(h->evs[0].second));   // the base event has been reached
+        // the other pool's launch may have started before the base event: a negative offset
+        if (hipEventElapsedTime(&at, h->evs[0].first, e.first) != hipSuccess) {
+          (void)hipGetLastError();
+          HIPCHK(hipEventElapsedTime(&at, e.first, h->evs[0].first));
+          at = -at;
+        }
+      }
+      iv.emplace_back((double)at, (double)at + ms);
+    } else {
+      h->kernel_ms += ms;
+    }
+  }
+  if (h->npools > 1) h->kernel_ms += interval_union(iv);
+  for (auto& e : h->evs) {
     (void)hipEventDestroy(e.first);
     (void)hipEventDestroy(e.second);
   }
@@ -927,16 +986,23 @@ static int flush_events(paxisim* h) {
 extern "C" int paxisim_destroy(paxisim* h) {
   if (!h) return 0;
   (void)hipSetDevice(h->cfg.device);
+  for (uint32_t p = 0; p < h->npools; p++)
+    if (h->pool[p].stream) (void)hipStreamSynchronize(h->pool[p].stream);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   flush_events(h);
   if (h->arena) (void)hipFree(h->arena);
   if (h->d_faults) (void)hipFree(h->d_faults);
   if (h->d_move) (void)hipFree(h->d_move);
-  if (h->d_ph) (void)hipFree(h->d_ph);
   if (h->d_scratch) (void)hipFree(h->d_scratch);
-  if (h->d_cmp) (void)hipFree(h->d_cmp);
-  if (h->d_pairs) (void)hipFree(h->d_pairs);
-  if (h->d_pipe) (void)hipFree(h->d_pipe);
+  for (Pool& pl : h->pool) {
+    if (pl.d_cmp) (void)hipFree(pl.d_cmp);
+    if (pl.d_pairs) (void)hipFree(pl.d_pairs);
+    if (pl.d_ph) (void)hipFree(pl.d_ph);
+    if (pl.d_pipe) (void)hipFree(pl.d_pipe);
+    if (pl.ev) (void)hipEventDestroy(pl.ev);
+    if (pl.stream && pl.stream != h->stream) (void)hipStreamDestroy(pl.stream);
+  }
+  if (h->ev_main) (void)hipEventDestroy(h->ev_main);
   if (h->P.lat_stamp) (void)hipFree(h->P.lat_stamp);
   if (h->P.lat_acc) (void)hipFree(h->P.lat_acc);
   if (h->d_lat_out) (void)hipFree(h->d_lat_out);
@@ -986,6 +1052,59 @@ static StepOps lat_step_ops_for(uint32_t protocol, uint32_t N, bool wlds, bool s
   if (protocol == PAXISIM_ABD) return pxs_lat::abd_step_ops(N);
   if (protocol == PAXISIM_EPAXOS) return pxs_lat::epaxos_step_ops(N);
   return pxs_lat::paxos_step_ops(N);
+}
+
+static hipError_t ensure_lds(paxisim* h);
+
+// Cluster pools.  Two pools only for a handle that compacts and runs pipelined
+// serial launches (Multi-Paxos); every other handle runs one.  PAXISIM_POOLS=1|2 decides; without it a
+// 5-replica handle takes two when its tiles are at least four times the resident wave slots (config 2:
+// 16,384 tiles against 2,048 slots, +2.7% in both mirrored pairs; no test-size handle).  The 9-replica
+// unit is left out by rule: config 4 measured -0.7% with two pools.  The split is a multiple of 8 tiles
+// as near the middle as that allows (pool_plan.h); if it leaves a region empty the handle runs one pool.
+static int pools_setup(paxisim* h) {
+  const Params& P = h->P;
+  const char* pe = getenv("PAXISIM_POOLS");
+  if (pe && strcmp(pe, "1") && strcmp(pe, "2")) return fail(PAXISIM_EINVAL, "PAXISIM_POOLS must be 1 or 2");
+  const bool can = P.compact && h->pipe_max > 1 && h->ops.serial && h->ops.launch_pipe;
+  const uint32_t tiles = (uint32_t)(P.C / LANES);
+  uint32_t want = 1;
+  if (pe) {
+    want = (uint32_t)atoi(pe);
+  } else if (can && P.N == 5) {
+    int dev = 0, cus = 0, per = 0;
+    if (ensure_lds(h) == hipSuccess && hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+        h->ops.occupancy(P, &per) == hipSuccess && cus > 0 && per > 0 && tiles >= 4u * (uint32_t)(cus * per))
+      want = 2;
+    (void)hipGetLastError();
+  }
+  const uint32_t split = can && want > 1 ? pool_split_tile(tiles, h->cfg.clusters) : 0u;
+  if (!split) return 0;
+  Pool& a = h->pool[0];
+  Pool& b = h->pool[1];
+  const size_t C = P.C;
+  a.end = b.base = split * LANES;
+  b.end = (uint32_t)C;
+  b.last_cmp = pool_first_cmp(1, h->S);
+  const size_t nblk = (C - b.base + CB - 1) / CB;
+  const size_t nq = 16 + (C / LANES > 64 ? C / LANES : 64);
+  hipError_t e;
+  a.stream = nullptr;
+  h->npools = 2;   // from here on paxisim_destroy frees what was made
+  if ((e = hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking)) != hipSuccess ||
+      (e = hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&a.ev, hipEventDisableTiming)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&b.ev, hipEventDisableTiming)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming)) != hipSuccess ||
+      (e = hipMalloc(&b.d_cmp, sizeof(uint32_t) * (CM_SUMS + nblk))) != hipSuccess ||
+      (e = hipMalloc(&b.d_pairs, sizeof(uint32_t) * 2 * (C / 2 + LANES))) != hipSuccess ||
+      (e = hipMalloc(&b.d_ph, sizeof(uint32_t) * (PH_SUMS + 2 * nblk))) != hipSuccess ||
+      (e = hipMalloc(&b.d_pipe, sizeof(uint32_t) * nq)) != hipSuccess ||
+      // the pipeline words of pool 0 with their spin limit; the error word starts clear
+      (e = hipMemcpyAsync(b.d_pipe, a.d_pipe, sizeof(uint32_t) * 16, hipMemcpyDeviceToDevice, h->stream)) != hipSuccess)
+    return fail(PAXISIM_EDEVICE, "cluster pool setup failed: %s", hipGetErrorString(e));
+  return 0;
 }
 
 extern "C" int paxisim_create(const paxisim_config* cfg, const paxisim_workload* wl, const paxisim_fault_process* fp,
@@ -1285,9 +1404,9 @@ extern "C" int paxisim_create(const paxisim_config* cfg, const paxisim_workload*
   const size_t ncmp = CM_SUMS + (cfg->clusters + CB - 1) / CB;
   if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess ||
       (e = hipMalloc(&h->d_scratch, sizeof(uint64_t) * 64)) != hipSuccess ||
-      (e = hipMalloc(&h->d_cmp, sizeof(uint32_t) * ncmp)) != hipSuccess ||
-      (e = hipMalloc(&h->d_pairs, sizeof(uint32_t) * 2 * (C / 2 + LANES))) != hipSuccess ||
-      (e = hipMalloc(&h->d_ph, sizeof(uint32_t) * (PH_SUMS + 2 * ((cfg->clusters + CB - 1) / CB)))) != hipSuccess ||
+      (e = hipMalloc(&h->pool[0].d_cmp, sizeof(uint32_t) * ncmp)) != hipSuccess ||
+      (e = hipMalloc(&h->pool[0].d_pairs, sizeof(uint32_t) * 2 * (C / 2 + LANES))) != hipSuccess ||
+      (e = hipMalloc(&h->pool[0].d_ph, sizeof(uint32_t) * (PH_SUMS + 2 * ((cfg->clusters + CB - 1) / CB)))) != hipSuccess ||
       (e = hipMalloc(&h->d_faults, sizeof(DevFault) * PAXISIM_MAX_FAULTS)) != hipSuccess ||
       (e = hipMemsetAsync(h->arena, 0, zero_bytes, h->stream)) != hipSuccess)
     rc1 = fail(PAXISIM_EDEVICE, "device setup failed: %s", hipGetErrorString(e));
@@ -1301,7 +1420,9 @@ extern "C" int paxisim_create(const paxisim_config* cfg, const paxisim_workload*
   h->wl.move_cdf = nullptr;
   if (!rc1) {
     P.faults = h->d_faults;
-    P.bound = h->d_cmp;
+    P.bound = h->pool[0].d_cmp;
+    h->pool[0].stream = h->stream;
+    h->pool[0].end = (uint32_t)C;
     // compaction: Paxos (the swap covers its arrays); PAXISIM_COMPACT=0 turns it off (A/B)
     const char* ce = getenv("PAXISIM_COMPACT");
     P.compact = cfg->protocol == PAXISIM_PAXOS && !(ce && atoi(ce) == 0);
@@ -1312,20 +1433,20 @@ extern "C" int paxisim_create(const paxisim_config* cfg, const paxisim_workload*
     if (h->pipe_max > 1 && h->ops.serial && h->ops.launch_pipe) {
       uint32_t xcc[64] = {0};
       const size_t nq = 16 + (C / LANES > 64 ? C / LANES : 64);   // the probe writes 64 words after the header
-      if ((e = hipMalloc(&h->d_pipe, sizeof(uint32_t) * nq)) != hipSuccess ||
-          (e = hipMemsetAsync(h->d_pipe, 0, sizeof(uint32_t) * 16, h->stream)) != hipSuccess)
+      if ((e = hipMalloc(&h->pool[0].d_pipe, sizeof(uint32_t) * nq)) != hipSuccess ||
+          (e = hipMemsetAsync(h->pool[0].d_pipe, 0, sizeof(uint32_t) * 16, h->stream)) != hipSuccess)
         rc1 = fail(PAXISIM_EDEVICE, "pipelined launch setup failed: %s", hipGetErrorString(e));
       if (!rc1) {
         // the poll limit of a chunk wait (sim_core.h pipe_item); PAXISIM_PIPE_SPIN sets it for tests
         uint32_t spin = PXS_PIPE_SPIN_DEFAULT;
         if (const char* se = getenv("PAXISIM_PIPE_SPIN")) spin = (uint32_t)strtoul(se, nullptr, 0);
-        if ((e = hipMemcpyAsync(h->d_pipe + 9, &spin, sizeof spin, hipMemcpyHostToDevice, h->stream)) != hipSuccess)
+        if ((e = hipMemcpyAsync(h->pool[0].d_pipe + 9, &spin, sizeof spin, hipMemcpyHostToDevice, h->stream)) != hipSuccess)
           rc1 = fail(PAXISIM_EDEVICE, "pipelined launch setup failed: %s", hipGetErrorString(e));
       }
       if (!rc1) {
-        xcc_probe<<<64, 64, 0, h->stream>>>(h->d_pipe + 16);
+        xcc_probe<<<64, 64, 0, h->stream>>>(h->pool[0].d_pipe + 16);
         if ((e = hipGetLastError()) != hipSuccess ||
-            (e = hipMemcpyAsync(xcc, h->d_pipe + 16, sizeof xcc, hipMemcpyDeviceToHost, h->stream)) != hipSuccess ||
+            (e = hipMemcpyAsync(xcc, h->pool[0].d_pipe + 16, sizeof xcc, hipMemcpyDeviceToHost, h->stream)) != hipSuccess ||
             (e = hipStreamSynchronize(h->stream)) != hipSuccess)
           rc1 = fail(PAXISIM_EDEVICE, "XCD probe failed: %s", hipGetErrorString(e));
         for (uint32_t b = 0; b < 64 && !rc1; b++)     // round robin over 8 XCDs, any rotation
@@ -1340,9 +1461,15 @@ extern "C" int paxisim_create(const paxisim_config* cfg, const paxisim_workload*
     // in the two run modes, every 50 +0.5 / +1.1%)
     if (h->pipe_max > 1 && h->ops.serial && h->ops.launch_pipe) h->cmp_every = (h->pipe_max < 3u ? h->pipe_max : 3u) * h->S;
     if (const char* ev = getenv("PAXISIM_COMPACT_EVERY")) h->cmp_every = (uint32_t)atoi(ev) ? (uint32_t)atoi(ev) : 1u;
-    const uint32_t b0 = (uint32_t)cfg->clusters;
+    if (const char* se = getenv("PAXISIM_PIPE_SLOTS")) h->pipe_slots = (uint32_t)strtoul(se, nullptr, 0);
+    if (!rc1) rc1 = pools_setup(h);
+    // every pool's bound: the clusters of its region
+    uint32_t b0 = (uint32_t)cfg->clusters;
     h->bound_host = b0;
-    e = hipMemcpyAsync(h->d_cmp, &b0, sizeof b0, hipMemcpyHostToDevice, h->stream);
+    for (uint32_t p = h->npools; p-- > 1 && e == hipSuccess;)
+      e = hipMemcpyAsync(h->pool[p].d_cmp, &b0, sizeof b0, hipMemcpyHostToDevice, h->stream);
+    if (h->npools > 1) b0 = h->pool[0].end;
+    if (e == hipSuccess) e = hipMemcpyAsync(h->pool[0].d_cmp, &b0, sizeof b0, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) init_kernel<<<(unsigned)((C + 255) / 256), 256, 0, h->stream>>>(P);
     if (e != hipSuccess || (e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(h->stream)) != hipSuccess)
       rc1 = fail(PAXISIM_EDEVICE, "init kernel failed: %s", hipGetErrorString(e));
@@ -1362,7 +1489,7 @@ extern "C" int paxisim_fault_add(paxisim* h, const paxisim_fault* f) {
     return fail(PAXISIM_EINVAL, "bad fault");
   if (f->kind == PAXISIM_FAULT_SLOW && f->param > h->cfg.max_delay)
     return fail(PAXISIM_EINVAL, "slow delay exceeds max_delay");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   h->faults.push_back(dev_fault(*f));
   HIPCHK(hipMemcpyAsync(h->d_faults, h->faults.data(), h->faults.size() * sizeof(DevFault),
                         hipMemcpyHostToDevice, h->stream));
@@ -1381,30 +1508,35 @@ static hipError_t ensure_lds(paxisim* h) {
   return hipSuccess;
 }
 
-static hipError_t launch_any(paxisim* h, uint32_t t0, uint32_t n) {
+static Region region_of(const paxisim* h, const Pool& pl) {
+  return Region{pl.base / LANES, (pl.end - pl.base) / LANES, pl.d_cmp, h->pipe_slots};
+}
+
+static hipError_t launch_any(paxisim* h, const Pool& pl, uint32_t t0, uint32_t n) {
   const hipError_t e = ensure_lds(h);
-  return e != hipSuccess ? e : h->ops.launch(h->P, h->stream, t0, n);
+  return e != hipSuccess ? e : h->ops.launch(h->P, pl.stream, t0, n, region_of(h, pl));
 }
 
 // After a pipelined launch every live tile must have run all K chunks; a tile
 // that did not (a wait that gave up, or waves missing from an XCD's queue)
 // sets the error word, which the host reads at the next sync (pipe_check).
-__global__ void pipe_verify(const uint32_t* bound, uint32_t* q, uint32_t K) {
-  const uint32_t tiles = (*bound + LANES - 1u) / LANES;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < tiles; i += gridDim.x * blockDim.x)
+__global__ void pipe_verify(const uint32_t* bound, uint32_t* q, uint32_t K, uint32_t tile0) {
+  const uint32_t tiles = (*bound + LANES - 1u) / LANES;   // the pool's live tiles: [tile0, tiles)
+  for (uint32_t i = tile0 + blockIdx.x * blockDim.x + threadIdx.x; i < tiles; i += gridDim.x * blockDim.x)
     if (q[16 + i] != K) atomicOr(&q[8], 2u);
 }
 
 // K chunks of n steps in one pipelined launch (sim_core.h sim_serial_pipe)
-static hipError_t launch_pipe(paxisim* h, uint32_t t0, uint32_t n, uint32_t K) {
+static hipError_t launch_pipe(paxisim* h, const Pool& pl, uint32_t t0, uint32_t n, uint32_t K) {
   hipError_t e = ensure_lds(h);          // the serial instances set both kernels' ceilings
   if (e != hipSuccess) return e;
+  const Region rg = region_of(h, pl);
   // tickets and chunk counts restart; the error word q[8] is sticky (cleared at create only)
-  if ((e = hipMemsetAsync(h->d_pipe, 0, sizeof(uint32_t) * 8, h->stream)) != hipSuccess ||
-      (e = hipMemsetAsync(h->d_pipe + 16, 0, sizeof(uint32_t) * (h->P.C / LANES), h->stream)) != hipSuccess)
+  if ((e = hipMemsetAsync(pl.d_pipe, 0, sizeof(uint32_t) * 8, pl.stream)) != hipSuccess ||
+      (e = hipMemsetAsync(pl.d_pipe + 16 + rg.tile0, 0, sizeof(uint32_t) * rg.tiles, pl.stream)) != hipSuccess)
     return e;
-  if ((e = h->ops.launch_pipe(h->P, h->stream, t0, n, K, h->d_pipe)) != hipSuccess) return e;
-  pipe_verify<<<64, 256, 0, h->stream>>>(h->P.bound, h->d_pipe, K);
+  if ((e = h->ops.launch_pipe(h->P, pl.stream, t0, n, K, pl.d_pipe, rg)) != hipSuccess) return e;
+  pipe_verify<<<64, 256, 0, pl.stream>>>(pl.d_cmp, pl.d_pipe, K, rg.tile0);
   return hipGetLastError();
 }
 
@@ -1413,11 +1545,14 @@ static hipError_t launch_pipe(paxisim* h, uint32_t t0, uint32_t n, uint32_t K) {
 // hipMemcpy would not wait for the launches in flight), so the word read is
 // the one every earlier launch left.  Every readout entry point calls this
 // first, so no caller gets stats or state of a step that did not fully run.
+// Each pool's words are read on that pool's stream; the error is the handle's, whichever pool set it.
 static int pipe_check(paxisim* h) {
-  if (!h->d_pipe) return 0;
+  if (!h->pool[0].d_pipe) return 0;
   uint32_t w[8] = {0};   // q[8..16): error word, spin limit, the first give-up
-  HIPCHK(hipMemcpyAsync(w, h->d_pipe + 8, sizeof w, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  for (uint32_t p = 0; p < h->npools && !w[0]; p++) {
+    HIPCHK(hipMemcpyAsync(w, h->pool[p].d_pipe + 8, sizeof w, hipMemcpyDeviceToHost, h->pool[p].stream));
+    HIPCHK(hipStreamSynchronize(h->pool[p].stream));
+  }
   if (!w[0]) return 0;
   if (w[0] & 1u)
     return fail(PAXISIM_EDEVICE, "pipelined step launch: a chunk wait timed out (xcd %u ticket %u tile %u chunk %u: "
@@ -1425,31 +1560,35 @@ static int pipe_check(paxisim* h) {
   return fail(PAXISIM_EDEVICE, "pipelined step launch: a tile missed chunks");
 }
 
-static int compact(paxisim* h) {
+// One pool's compaction at step t, on the pool's stream: its region's slots only.
+static int compact(paxisim* h, Pool& pl, uint32_t t) {
   const Params& P = h->P;
-  const unsigned nb = (unsigned)((h->cfg.clusters + CB - 1) / CB);
-  uint32_t* lo = h->d_pairs;
-  uint32_t* hi = h->d_pairs + (P.C / 2 + LANES);
-  cmp_count<<<nb, CB, 0, h->stream>>>(P, h->d_cmp);
-  cmp_scan<<<1, CB, 0, h->stream>>>(P, h->d_cmp, nb);
-  cmp_index<<<nb, CB, 0, h->stream>>>(P, h->d_cmp, lo, hi);
-  cmp_swap<<<4096, LANES, 0, h->stream>>>(P, h->d_cmp, lo, hi);
-  cmp_freeze<<<nb, CB, 0, h->stream>>>(P, h->d_cmp, h->t);
-  cmp_setbound<<<1, 1, 0, h->stream>>>(h->d_cmp);
+  const uint64_t top = pl.end < h->cfg.clusters ? pl.end : h->cfg.clusters;   // the region's clusters end here
+  const unsigned nb = (unsigned)((top - pl.base + CB - 1) / CB);
+  const uint32_t base = pl.base;
+  uint32_t* lo = pl.d_pairs;
+  uint32_t* hi = pl.d_pairs + (P.C / 2 + LANES);
+  hipStream_t st = pl.stream;
+  cmp_count<<<nb, CB, 0, st>>>(P, pl.d_cmp, base);
+  cmp_scan<<<1, CB, 0, st>>>(P, pl.d_cmp, nb, base);
+  cmp_index<<<nb, CB, 0, st>>>(P, pl.d_cmp, lo, hi, base);
+  cmp_swap<<<4096, LANES, 0, st>>>(P, pl.d_cmp, lo, hi);
+  cmp_freeze<<<nb, CB, 0, st>>>(P, pl.d_cmp, t, base);
+  cmp_setbound<<<1, 1, 0, st>>>(pl.d_cmp);
   if (P.phase_sort) {   // group the stepped slots by phase class
-    uint32_t* ph = h->d_ph;
-    HIPCHK(hipMemsetAsync(ph, 0, PH_SUMS * sizeof(uint32_t), h->stream));
-    ph_classes<<<nb, CB, 0, h->stream>>>(P, h->d_cmp, ph);
+    uint32_t* ph = pl.d_ph;
+    HIPCHK(hipMemsetAsync(ph, 0, PH_SUMS * sizeof(uint32_t), st));
+    ph_classes<<<nb, CB, 0, st>>>(P, pl.d_cmp, ph, base);
     for (uint32_t p = 0; p < P.phase_period; p++) {   // classes 0..period-1; the quiescent ones end up last
-      ph_region<<<1, 1, 0, h->stream>>>(ph, p);
-      ph_count<<<nb, CB, 0, h->stream>>>(P, h->d_cmp, ph, p, nb);
-      ph_scan<<<1, CB, 0, h->stream>>>(h->d_cmp, ph, nb);
-      ph_index<<<nb, CB, 0, h->stream>>>(P, h->d_cmp, ph, p, nb, lo, hi);
-      cmp_swap<<<4096, LANES, 0, h->stream>>>(P, h->d_cmp, lo, hi);
+      ph_region<<<1, 1, 0, st>>>(ph, p, base);
+      ph_count<<<nb, CB, 0, st>>>(P, pl.d_cmp, ph, p, nb, base);
+      ph_scan<<<1, CB, 0, st>>>(pl.d_cmp, ph, nb);
+      ph_index<<<nb, CB, 0, st>>>(P, pl.d_cmp, ph, p, nb, lo, hi, base);
+      cmp_swap<<<4096, LANES, 0, st>>>(P, pl.d_cmp, lo, hi);
     }
   }
   HIPCHK(hipGetLastError());
-  h->last_cmp = h->t;
+  pl.last_cmp = t;
   return 0;
 }
 
@@ -1457,19 +1596,25 @@ static int compact(paxisim* h) {
 // fault process of that slot's tile up to now and step the tile again.
 static int wake(paxisim* h, uint64_t cluster) {
   const Params& P = h->P;
-  uint32_t bound = 0, slot = 0;
-  HIPCHK(hipMemcpyAsync(&bound, h->d_cmp + CM_BOUND, 4, hipMemcpyDeviceToHost, h->stream));
+  uint32_t bounds[MAX_POOLS] = {0, 0}, slot = 0;
+  for (uint32_t p = 0; p < h->npools; p++)
+    HIPCHK(hipMemcpyAsync(&bounds[p], h->pool[p].d_cmp + CM_BOUND, 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(&slot, P.slot_of + cluster, 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  // the pool whose region holds the slot: the cluster wakes there, at that pool's bound
+  const uint32_t wp = h->npools > 1 && slot >= h->pool[1].base ? 1u : 0u;
+  const Pool& pl = h->pool[wp];
+  const uint32_t bound = bounds[wp];
   h->bound_host = bound;
   if (slot < bound) return 0;
   if (slot != bound) swap_one<<<1, LANES, 0, h->stream>>>(P, bound, slot);
   uint64_t end = (uint64_t)bound + LANES;
+  if (end > pl.end) end = pl.end;
   if (end > h->cfg.clusters) end = h->cfg.clusters;
   const uint64_t n = (end - bound) * P.N;
   replay_kernel<<<(unsigned)((n + 63) / 64), 64, 0, h->stream>>>(P, bound, end, h->t);
   const uint32_t nb32 = (uint32_t)end;
-  HIPCHK(hipMemcpyAsync(h->d_cmp + CM_BOUND, &nb32, 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(pl.d_cmp + CM_BOUND, &nb32, 4, hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));
   h->bound_host = nb32;
@@ -1494,7 +1639,7 @@ extern "C" int paxisim_read_client(paxisim* h, uint64_t cluster, paxisim_worker_
                                    uint32_t* n_out) {
   if (!h || !n_out || (cap && !out)) return fail(PAXISIM_EINVAL, "null argument");
   if (cluster >= h->cfg.clusters) return fail(PAXISIM_ERANGE, "bad cluster");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   const uint32_t n = h->P.WK;
   *n_out = n;
@@ -1529,7 +1674,7 @@ extern "C" int paxisim_read_kv(paxisim* h, uint64_t cluster, uint32_t replica, u
   if (cluster >= h->cfg.clusters || replica >= h->P.N || n > h->P.keys) return fail(PAXISIM_ERANGE, "bad key range");
   if (h->P.protocol != PAXISIM_ABD && !h->P.kv) return fail(PAXISIM_EUNSUPP, "replicas keep no Database (config.kv = 0)");
   if (n == 0) return 0;
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   uint32_t* d = nullptr;
   HIPCHK(hipMalloc(&d, n * sizeof(uint32_t)));
@@ -1544,21 +1689,24 @@ extern "C" int paxisim_read_kv(paxisim* h, uint64_t cluster, uint32_t replica, u
 
 extern "C" int paxisim_active_clusters(paxisim* h, uint64_t* active) {
   if (!h || !active) return fail(PAXISIM_EINVAL, "null argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
-  uint32_t bound = 0;
-  HIPCHK(hipMemcpyAsync(&bound, h->d_cmp + CM_BOUND, 4, hipMemcpyDeviceToHost, h->stream));
+  uint32_t bounds[MAX_POOLS] = {0, 0}, bound = 0;
+  for (uint32_t p = 0; p < h->npools; p++)
+    HIPCHK(hipMemcpyAsync(&bounds[p], h->pool[p].d_cmp + CM_BOUND, 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  for (uint32_t p = 0; p < h->npools; p++) bound += bounds[p] - h->pool[p].base;   // the pools' stepped slots
   h->bound_host = bound;
   *active = bound;
   return 0;
 }
 
-__global__ void activity_kernel(Params P, uint64_t lo, uint64_t n, uint32_t* out) {
+// b1, base1: the second pool's bound and first slot (one pool: base1 past every slot)
+__global__ void activity_kernel(Params P, uint64_t lo, uint64_t n, uint32_t* out, const uint32_t* b1, uint64_t base1) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint64_t s = slot_of(P, lo + i);
-  out[i] = s < *P.bound ? 0xFFFFFFFFu : P.frz[s];
+  out[i] = s < (s < base1 ? *P.bound : *b1) ? 0xFFFFFFFFu : P.frz[s];
 }
 
 extern "C" int paxisim_quorum(const paxisim_config* cfg, uint32_t kind, uint32_t ack_mask, int* satisfied) {
@@ -1580,11 +1728,12 @@ extern "C" int paxisim_read_activity(paxisim* h, uint64_t lo, uint64_t n, uint32
   if (!h || !frozen_at) return fail(PAXISIM_EINVAL, "null argument");
   if (lo + n > h->cfg.clusters || lo + n < lo) return fail(PAXISIM_ERANGE, "cluster range");
   if (n == 0) return 0;
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   uint32_t* d = nullptr;
   HIPCHK(hipMalloc(&d, n * sizeof(uint32_t)));
-  activity_kernel<<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(h->P, lo, n, d);
+  activity_kernel<<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(
+      h->P, lo, n, d, h->npools > 1 ? h->pool[1].d_cmp : h->P.bound, h->npools > 1 ? (uint64_t)h->pool[1].base : ~0ull);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(frozen_at, d, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -1597,14 +1746,27 @@ extern "C" int paxisim_step(paxisim* h, uint32_t nsteps) {
   if (!h) return fail(PAXISIM_EINVAL, "null handle");
   if ((uint64_t)h->t + nsteps >= T_MAX) return fail(PAXISIM_EINVAL, "step counter would exceed 2^28");
   HIPCHK(hipSetDevice(h->cfg.device));
-  while (nsteps > 0) {
-    const uint32_t n = nsteps < h->S ? nsteps : h->S;
-    // chunks fused into this launch: up to pipe_max whole chunks, none past a due compaction
-    uint32_t K = 1;
-    if (h->pipe_max > 1 && n == h->S) {
-      auto due = [&](uint32_t t) { return h->P.compact && t >= h->late_until && t - h->last_cmp >= h->cmp_every; };
-      while (K < h->pipe_max && (K + 1u) * n <= nsteps && !due(h->t + K * n)) K++;
-    }
+  if (h->npools > 1 && h->main_ahead) {   // the pools' streams wait for what the handle's stream did since
+    HIPCHK(hipEventRecord(h->ev_main, h->stream));
+    for (uint32_t p = 0; p < h->npools; p++) HIPCHK(hipStreamWaitEvent(h->pool[p].stream, h->ev_main, 0));
+    h->main_ahead = false;
+  }
+  // every pool's launches of this call (pool_plan.h): chunks fused up to pipe_max, none past a due
+  // compaction of that pool; all pools end at h->t + nsteps.  Nothing here waits for the device
+  // or makes one pool's stream wait for the other's.
+  PoolPlanIn in;
+  in.t = h->t;
+  in.nsteps = nsteps;
+  in.S = h->S;
+  in.pipe_max = h->pipe_max;
+  in.cmp_every = h->cmp_every;
+  in.late_until = h->late_until;
+  in.compact = h->P.compact != 0;
+  in.npools = h->npools;
+  for (uint32_t p = 0; p < h->npools; p++) in.last_cmp[p] = h->pool[p].last_cmp;
+  h->pools_ahead = true;
+  for (const PoolLaunch& L : pool_plan(in)) {
+    Pool& pl = h->pool[L.pool];
     hipEvent_t a, b;
     HIPCHK(hipEventCreate(&a));
     hipError_t e = hipEventCreate(&b);
@@ -1612,9 +1774,9 @@ extern "C" int paxisim_step(paxisim* h, uint32_t nsteps) {
       (void)hipEventDestroy(a);
       return fail(PAXISIM_EDEVICE, "hipEventCreate: %s", hipGetErrorString(e));
     }
-    if ((e = hipEventRecord(a, h->stream)) == hipSuccess &&
-        (e = K > 1 ? launch_pipe(h, h->t, n, K) : launch_any(h, h->t, n)) == hipSuccess)
-      e = hipEventRecord(b, h->stream);
+    if ((e = hipEventRecord(a, pl.stream)) == hipSuccess &&
+        (e = L.chunks > 1 ? launch_pipe(h, pl, L.t0, L.n, L.chunks) : launch_any(h, pl, L.t0, L.n)) == hipSuccess)
+      e = hipEventRecord(b, pl.stream);
     if (e != hipSuccess) {              // no leaked events on the error path
       (void)hipEventDestroy(a);
       (void)hipEventDestroy(b);
@@ -1622,10 +1784,8 @@ extern "C" int paxisim_step(paxisim* h, uint32_t nsteps) {
     }
     h->evs.emplace_back(a, b);
     h->launches++;
-    h->t += K * n;
-    nsteps -= K * n;
-    if (h->P.compact && h->t >= h->late_until && h->t - h->last_cmp >= h->cmp_every) {
-      const int rc = compact(h);
+    if (L.compact) {
+      const int rc = compact(h, pl, L.t0 + L.chunks * L.n);
       if (rc) return rc;
     }
     if (h->evs.size() >= 256) {
@@ -1633,19 +1793,21 @@ extern "C" int paxisim_step(paxisim* h, uint32_t nsteps) {
       if (rc) return rc;
     }
   }
+  h->t += nsteps;
   return 0;
 }
 
 extern "C" int paxisim_sync(paxisim* h) {
   if (!h) return fail(PAXISIM_EINVAL, "null handle");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
+  for (uint32_t p = 0; p < h->npools; p++) HIPCHK(hipStreamSynchronize(h->pool[p].stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return pipe_check(h);
 }
 
 extern "C" int paxisim_kernel_time(paxisim* h, double* ms, uint64_t* launches, int reset) {
   if (!h) return fail(PAXISIM_EINVAL, "null handle");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   int rc = flush_events(h);
   if (rc) return rc;
   if (ms) *ms = h->kernel_ms;
@@ -1662,7 +1824,7 @@ extern "C" int paxisim_inject(paxisim* h, uint64_t cluster, uint32_t replica, ui
   if (cluster >= h->cfg.clusters || replica >= h->P.N || cid < 1 || cid > CMD_MASK)
     return fail(PAXISIM_EINVAL, "bad inject (cluster %llu, replica %u, cid %u)", (unsigned long long)cluster,
                 replica, cid);
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (h->P.compact) {
     const int rc = wake(h, cluster);
     if (rc) return rc;
@@ -1680,7 +1842,7 @@ extern "C" int paxisim_read_inbox(paxisim* h, uint64_t cluster, uint32_t replica
                                   uint32_t cap, uint32_t* n_out) {
   if (!h || !n_out || (cap && !out)) return fail(PAXISIM_EINVAL, "null argument");
   if (cluster >= h->cfg.clusters || replica >= h->P.N) return fail(PAXISIM_ERANGE, "bad inbox");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   HIPCHK(hipStreamSynchronize(h->stream));
   const uint32_t maxn = h->P.NS * h->P.M;   // a bucket set holds at most this many
@@ -1705,7 +1867,7 @@ extern "C" int paxisim_commands(paxisim* h, uint64_t cluster, const uint32_t* ci
   if (!h || (n && (!cids || !keys || !writes))) return fail(PAXISIM_EINVAL, "null argument");
   if (cluster >= h->cfg.clusters) return fail(PAXISIM_ERANGE, "bad cluster");
   if (n == 0) return 0;
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   uint32_t* d = nullptr;
   HIPCHK(hipMalloc(&d, 3ull * n * sizeof(uint32_t)));
@@ -1730,7 +1892,7 @@ extern "C" int paxisim_deliver(paxisim* h, uint64_t cluster, uint32_t replica, u
                 replica, src);
   if (n == 0) return 0;
   if (n > h->P.M) return fail(PAXISIM_EINVAL, "mailbox full");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (h->P.compact) {
     const int rc = wake(h, cluster);
     if (rc) return rc;
@@ -1757,7 +1919,7 @@ extern "C" int paxisim_read_log(paxisim* h, uint64_t cluster, uint32_t replica, 
   if (!h || !out) return fail(PAXISIM_EINVAL, "null argument");
   if (cluster >= h->cfg.clusters || replica >= h->P.N || key >= h->P.NK) return fail(PAXISIM_ERANGE, "bad entry");
   if (n == 0) return 0;
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   paxisim_log_entry* d = nullptr;
   HIPCHK(hipMalloc(&d, n * sizeof(paxisim_log_entry)));
@@ -1773,7 +1935,7 @@ extern "C" int paxisim_read_log(paxisim* h, uint64_t cluster, uint32_t replica, 
 
 extern "C" int paxisim_stats_get(paxisim* h, paxisim_stats* out) {
   if (!h || !out) return fail(PAXISIM_EINVAL, "null argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   uint64_t red[NRED];
   HIPCHK(hipMemsetAsync(h->d_scratch, 0, sizeof(uint64_t) * NRED, h->stream));
@@ -1805,7 +1967,7 @@ extern "C" int paxisim_read_state(paxisim* h, uint64_t lo, uint64_t n, paxisim_r
   if (!h || !out) return fail(PAXISIM_EINVAL, "null argument");
   if (lo + n > h->cfg.clusters || lo + n < lo) return fail(PAXISIM_ERANGE, "cluster range");
   if (n == 0) return 0;
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   const size_t cnt = (size_t)n * h->P.N;
   paxisim_replica_state* d = nullptr;
@@ -1824,7 +1986,7 @@ extern "C" int paxisim_read_instances(paxisim* h, uint64_t lo, uint64_t n, paxis
   if (!h || !out) return fail(PAXISIM_EINVAL, "null argument");
   if (lo + n > h->cfg.clusters || lo + n < lo) return fail(PAXISIM_ERANGE, "cluster range");
   if (n == 0) return 0;
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   const uint32_t ni = h->P.protocol == PAXISIM_EPAXOS ? h->P.N * h->P.N : h->P.NI;   // per cluster; EPaxos: (replica, owner log)
   const size_t cnt = (size_t)n * ni;
@@ -1842,7 +2004,7 @@ extern "C" int paxisim_read_instances(paxisim* h, uint64_t lo, uint64_t n, paxis
 
 extern "C" int paxisim_check(paxisim* h, uint64_t* violations) {
   if (!h || !violations) return fail(PAXISIM_EINVAL, "null argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   HIPCHK(hipMemsetAsync(h->d_scratch, 0, sizeof(uint64_t), h->stream));
   check_kernel<<<(unsigned)(h->P.C / 256 + 1), 256, 0, h->stream>>>(h->P, h->d_scratch);
@@ -1854,7 +2016,7 @@ extern "C" int paxisim_check(paxisim* h, uint64_t* violations) {
 
 extern "C" int paxisim_occupancy(paxisim* h, int* blocks_per_cu, uint32_t* lds_bytes, uint32_t* staged) {
   if (!h || !blocks_per_cu) return fail(PAXISIM_EINVAL, "null argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   HIPCHK(h->ops.occupancy(h->P, blocks_per_cu));
   *blocks_per_cu *= (int)h->P.G;    // 64-cluster tiles resident per CU
   if (lds_bytes) *lds_bytes = h->P.lds_bytes;
@@ -1879,7 +2041,7 @@ extern "C" int paxisim_latency_enable(paxisim* h, uint32_t bins) {
     return fail(PAXISIM_EINVAL, "latency bins must be a power of two in [16, %u]", PAXISIM_LAT_MAX_BINS);
   if (h->P.lat_bins) return fail(PAXISIM_EINVAL, "latency is already enabled");
   if (h->t) return fail(PAXISIM_EINVAL, "latency can only be enabled before the first step");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   // the recording build of the handle's kernel: the same instance, so the launch shape chosen at create fits it
   const StepOps ops = lat_step_ops_for(h->P.protocol, h->P.N, h->P.wlds != 0, h->ops.serial);
   int vgprs = 0, maxthr = 0;
@@ -1913,7 +2075,7 @@ extern "C" int paxisim_latency_enable(paxisim* h, uint32_t bins) {
 extern "C" int paxisim_latency_reset(paxisim* h) {
   if (!h) return fail(PAXISIM_EINVAL, "null handle");
   if (!h->P.lat_bins) return fail(PAXISIM_EINVAL, "latency is not enabled");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   // on the launch stream: after every step launched so far, before the next one
   HIPCHK(hipMemsetAsync(h->P.lat_acc, 0, sizeof(unsigned long long) * lat_acc_words(h->P), h->stream));
   return 0;
@@ -1923,7 +2085,7 @@ extern "C" int paxisim_latency_get(paxisim* h, uint32_t worker, paxisim_latency*
   if (!h || !out) return fail(PAXISIM_EINVAL, "null argument");
   if (!h->P.lat_bins) return fail(PAXISIM_EINVAL, "latency is not enabled");
   if (worker != PAXISIM_ALL_WORKERS && worker >= h->P.WK) return fail(PAXISIM_EINVAL, "no worker %u", worker);
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   const uint32_t bins = h->P.lat_bins;
   const size_t row = lat_row(bins), n = (size_t)h->P.WK * row;
@@ -1993,7 +2155,7 @@ extern "C" int paxisim_latency_stat_of(const paxisim_latency* l, const uint64_t*
 extern "C" int paxisim_history(paxisim* h, uint64_t cluster, uint32_t* buf, uint32_t cap_ops, uint32_t* n_out) {
   if (!h || !n_out) return fail(PAXISIM_EINVAL, "null argument");
   if (cluster >= h->cfg.clusters) return fail(PAXISIM_ERANGE, "cluster");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   HIPCHK(hipStreamSynchronize(h->stream));   // step kernels run on the non-blocking h->stream
   const Params& P = h->P;
@@ -2026,7 +2188,7 @@ extern "C" int paxisim_history_load(paxisim* h, uint64_t cluster, uint32_t repli
   if (cluster >= h->cfg.clusters || replica >= h->P.N) return fail(PAXISIM_ERANGE, "bad replica");
   if (h->P.protocol != PAXISIM_ABD) return fail(PAXISIM_EUNSUPP, "op history is kept by ABD only");
   if (n > h->P.H) return fail(PAXISIM_EINVAL, "%u ops exceed history capacity %u", n, h->P.H);
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   HIPCHK(hipStreamSynchronize(h->stream));
   const Params& P = h->P;
   std::vector<uint4> tmp(n ? n : 1);
@@ -2046,7 +2208,7 @@ extern "C" int paxisim_history_load(paxisim* h, uint64_t cluster, uint32_t repli
 // replicas' completed ABD ops, or LinClient, the workers' ops of any protocol (chist_kernel.h).
 template <class S>
 static int lin_scan(paxisim* h, uint64_t* anomalies, uint64_t* ops, uint64_t* skipped) {
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   HIPCHK(hipStreamSynchronize(h->stream));
   const Params& P = h->P;
@@ -2145,7 +2307,7 @@ extern "C" int paxisim_client_history_enable(paxisim* h, uint32_t ops_per_worker
                                 "call paxisim_latency_enable first");
   if (h->P.protocol != PAXISIM_ABD && !h->P.kv)
     return fail(PAXISIM_EUNSUPP, "replies carry no read values (config.kv = 0)");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   Params P = h->P;
   P.ch_cap = ops_per_worker;
   const size_t cb = sizeof(uint32_t) * P.WK * P.C, ob = sizeof(uint4) * P.WK * P.C * (size_t)ops_per_worker;
@@ -2169,7 +2331,7 @@ extern "C" int paxisim_client_history(paxisim* h, uint64_t cluster, uint32_t* bu
   if (!h || !n_out) return fail(PAXISIM_EINVAL, "null argument");
   if (!h->P.ch_cap) return fail(PAXISIM_EINVAL, "the client history is not enabled");
   if (cluster >= h->cfg.clusters) return fail(PAXISIM_ERANGE, "cluster");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   const Params& P = h->P;
   const uint32_t tot = P.WK * P.ch_cap;
@@ -2216,7 +2378,7 @@ extern "C" int paxisim_client_history_load(paxisim* h, uint64_t cluster, uint32_
   if (!h->P.ch_cap) return fail(PAXISIM_EINVAL, "the client history is not enabled");
   if (cluster >= h->cfg.clusters || worker >= h->P.WK) return fail(PAXISIM_ERANGE, "bad worker");
   if (n > h->P.ch_cap) return fail(PAXISIM_EINVAL, "%u ops exceed history capacity %u", n, h->P.ch_cap);
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;
   HIPCHK(hipStreamSynchronize(h->stream));
   const Params& P = h->P;
@@ -2252,7 +2414,7 @@ extern "C" int paxisim_multiversion_enable(paxisim* h, uint32_t versions_per_key
   if (h->P.protocol == PAXISIM_ABD)
     return fail(PAXISIM_EUNSUPP, "ABD's KV is written by versioned Sets, not by Execute of a log: no put order to record");
   if (!h->P.kv) return fail(PAXISIM_EUNSUPP, "replicas keep no Database (config.kv = 0)");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   Params P = h->P;
   P.mv_cap = versions_per_key;
   const size_t rows = (size_t)P.keys * P.N * P.C;
@@ -2278,7 +2440,7 @@ extern "C" int paxisim_kv_history(paxisim* h, uint64_t cluster, uint32_t replica
   if (!h->P.mv_cap) return fail(PAXISIM_EINVAL, "multiversion is not enabled");
   if (cluster >= h->cfg.clusters) return fail(PAXISIM_ERANGE, "cluster");
   if (replica >= h->P.N || key >= h->P.keys) return fail(PAXISIM_EINVAL, "no replica %u or key %u", replica, key);
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   const Params& P = h->P;
   const size_t row = mv_row(P, key, replica, cluster);
@@ -2298,7 +2460,7 @@ extern "C" int paxisim_kv_history(paxisim* h, uint64_t cluster, uint32_t replica
 // client.go:279-320 over clusters [lo, lo + n): totals into tot[MV_NOUT], the failing keys of each
 // cluster into masks (either may be null).
 static int mv_scan(paxisim* h, uint64_t lo, uint64_t n, uint64_t* tot, uint64_t* masks) {
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   const Params& P = h->P;
   unsigned long long* d_masks = nullptr;
@@ -2418,7 +2580,7 @@ extern "C" int paxisim_dist_unique_id(unsigned char id[128]) {
 static int dist_alloc(paxisim_dist* d) {
   for (paxisim* h : d->h) {
     void* b = nullptr;
-    HIPCHK(hipSetDevice(h->cfg.device));
+    if (const int jrc = enter(h)) return jrc;
     HIPCHK(hipMalloc(&b, 2 * DIST_MAXV * sizeof(uint64_t)));
     d->buf.push_back(b);
   }
@@ -2472,7 +2634,7 @@ extern "C" int paxisim_dist_init_rank(paxisim* h, const unsigned char id[128], i
                                       paxisim_dist** out) {
   if (!h || !id || nranks < 1 || rank < 0 || rank >= nranks || !out) return fail(PAXISIM_EINVAL, "bad argument");
   if (!rccl().ok) return fail(PAXISIM_EUNSUPP, "RCCL (librccl.so.1) not available");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   paxisim_dist* d = new (std::nothrow) paxisim_dist();
   if (!d) return fail(PAXISIM_ENOMEM, "oom");
   d->h.push_back(h);
@@ -2504,7 +2666,7 @@ extern "C" int paxisim_dist_allreduce(paxisim_dist* d, const uint64_t* sums_in, 
   const size_t k = d->h.size();
   for (size_t i = 0; i < k; i++) {
     paxisim* h = d->h[i];
-    HIPCHK(hipSetDevice(h->cfg.device));
+    if (const int jrc = enter(h)) return jrc;
     uint64_t* b = static_cast<uint64_t*>(d->buf[i]);
     if (n) HIPCHK(hipMemcpyAsync(b, sums_in + i * n, n * 8, hipMemcpyHostToDevice, h->stream));
     if (m) HIPCHK(hipMemcpyAsync(b + DIST_MAXV, maxes_in + i * m, m * 8, hipMemcpyHostToDevice, h->stream));
@@ -2518,7 +2680,7 @@ extern "C" int paxisim_dist_allreduce(paxisim_dist* d, const uint64_t* sums_in, 
   RCCLCHK(rccl().group_end());
   for (size_t i = 0; i < k; i++) {
     paxisim* h = d->h[i];
-    HIPCHK(hipSetDevice(h->cfg.device));
+    if (const int jrc = enter(h)) return jrc;
     uint64_t* b = static_cast<uint64_t*>(d->buf[i]);
     if (i == 0 && n) HIPCHK(hipMemcpyAsync(sums_out, b, n * 8, hipMemcpyDeviceToHost, h->stream));
     if (i == 0 && m) HIPCHK(hipMemcpyAsync(maxes_out, b + DIST_MAXV, m * 8, hipMemcpyDeviceToHost, h->stream));
@@ -2562,14 +2724,14 @@ constexpr uint32_t DBG_PER = 48;   // the stamps build's buffer size (paxisim_de
 // (PXS_STAMPS), per block the serial kernel's start and end clock (PXS_WAVE_TIMES, tools/wave_times.py), or
 // per block the access-class tallies (PXS_TALLY, tools/tally.py).
 extern "C" int paxisim_dbg_enable(paxisim* h) {
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   const size_t n = (h->P.C / LANES) * 16 * DBG_PER;
   HIPCHK(hipMalloc(&h->P.dbg, n * 8));
   HIPCHK(hipMemset(h->P.dbg, 0, n * 8));
   return 0;
 }
 extern "C" int paxisim_dbg_read(paxisim* h, unsigned long long* out) {
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int jrc = enter(h)) return jrc;
   HIPCHK(hipStreamSynchronize(h->stream));
   const size_t n = (h->P.C / LANES) * 16 * DBG_PER;
   HIPCHK(hipMemcpy(out, h->P.dbg, n * 8, hipMemcpyDeviceToHost));

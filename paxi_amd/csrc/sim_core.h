@@ -1656,6 +1656,20 @@ __global__ void __launch_bounds__(LANES, serial_waves<Proto>()) sim_serial(Param
   serial_tile<NT, Proto>(P, blk, bound, t0, nsteps, lds);
 }
 
+// The same over a pool's slot region: tiles from tile0 on, live below the pool's
+// bound (an absolute slot index).  A kernel of its own, instantiated for Multi-Paxos only
+// (step_ops.h), so that a handle of one pool runs exactly the kernels above: an extra argument in
+// them cost the 9-replica unit 2% on config 4 and moved the WPaxos unit's register allocation.
+template <int NT, class Proto>
+__global__ void __launch_bounds__(LANES, serial_waves<Proto>()) sim_serial_region(Params P, uint32_t t0, uint32_t nsteps,
+                                                                                 uint32_t tile0, const uint32_t* boundp) {
+  extern __shared__ uint4 lds[];
+  const uint32_t bound = __builtin_amdgcn_readfirstlane(*boundp);
+  const uint32_t blk = tile0 + blockIdx.x;
+  if ((uint64_t)blk * LANES >= bound) return;
+  serial_tile<NT, Proto>(P, blk, bound, t0, nsteps, lds);
+}
+
 // The pipelined serial kernel: K chunks of nsteps steps of
 // every live tile in one launch, so a slot freed by a tile that finishes its
 // chunk takes the next ready (tile, chunk) instead of idling until the last
@@ -1691,14 +1705,15 @@ __global__ void __launch_bounds__(LANES, serial_waves<Proto>()) sim_serial(Param
 #define PXS_PIPE_SPIN_DEFAULT (1u << 22)   // polls of ~2 us: seconds, against chunks of at most ~0.1 s
 template <int NT, class Proto>
 __device__ __forceinline__ bool pipe_item(const Params& P, uint32_t t0, uint32_t nsteps, uint32_t K, uint32_t* q,
-                                          uint32_t bound, uint32_t xcd, uint32_t tx, uint32_t spin_max, uint4* lds) {
+                                          uint32_t bound, uint32_t tile0, uint32_t xcd, uint32_t tx, uint32_t spin_max,
+                                          uint4* lds) {
   uint32_t it = 0;
   if (threadIdx.x == 0) it = atomicAdd(&q[xcd], 1u);
   it = __builtin_amdgcn_readfirstlane(it);
   if (it >= tx * K) return false;
   // uniform by construction; said so, so the tile's addressing stays in scalar registers
   const uint32_t c = __builtin_amdgcn_readfirstlane(it / tx);
-  const uint32_t blk = __builtin_amdgcn_readfirstlane(xcd + 8u * (it - c * tx));
+  const uint32_t blk = __builtin_amdgcn_readfirstlane(tile0 + xcd + 8u * (it - c * tx));
   uint32_t* done = q + 16;
   if (c) {
     uint32_t spins = 0;
@@ -1742,9 +1757,29 @@ __global__ void __launch_bounds__(LANES, serial_waves<Proto>()) sim_serial_pipe(
   if constexpr (PXS_PIPE_PERSIST) {
     // every iteration takes a new ticket, so a wave runs at most tx * K items (a bound, not a guess)
     for (uint32_t n = 0; n <= tx * K; n++)
-      if (!pipe_item<NT, Proto>(P, t0, nsteps, K, q, bound, xcd, tx, spin_max, lds)) break;
+      if (!pipe_item<NT, Proto>(P, t0, nsteps, K, q, bound, 0u, xcd, tx, spin_max, lds)) break;
   } else {
-    pipe_item<NT, Proto>(P, t0, nsteps, K, q, bound, xcd, tx, spin_max, lds);
+    pipe_item<NT, Proto>(P, t0, nsteps, K, q, bound, 0u, xcd, tx, spin_max, lds);
+  }
+}
+
+// sim_serial_pipe over a pool's slot region (see sim_serial_region): its live tiles are
+// [tile0, ceil(bound / 64)), tile0 a multiple of 8, so tile i of the region still belongs to XCD i mod 8.
+template <int NT, class Proto>
+__global__ void __launch_bounds__(LANES, serial_waves<Proto>()) sim_serial_pipe_region(
+    Params P, uint32_t t0, uint32_t nsteps, uint32_t K, uint32_t* q, uint32_t tile0, const uint32_t* boundp) {
+  extern __shared__ uint4 lds[];
+  const uint32_t bound = __builtin_amdgcn_readfirstlane(*boundp);
+  const uint32_t top = (bound + LANES - 1u) / LANES;
+  const uint32_t tiles = top > tile0 ? top - tile0 : 0u;
+  const uint32_t xcd = __builtin_amdgcn_s_getreg((20) | (0 << 6) | ((32 - 1) << 11)) & 7u;   // HW_REG_XCC_ID
+  const uint32_t tx = tiles > xcd ? (tiles - xcd + 7u) / 8u : 0u;
+  const uint32_t spin_max = __builtin_amdgcn_readfirstlane(q[9]);
+  if constexpr (PXS_PIPE_PERSIST) {
+    for (uint32_t n = 0; n <= tx * K; n++)
+      if (!pipe_item<NT, Proto>(P, t0, nsteps, K, q, bound, tile0, xcd, tx, spin_max, lds)) break;
+  } else {
+    pipe_item<NT, Proto>(P, t0, nsteps, K, q, bound, tile0, xcd, tx, spin_max, lds);
   }
 }
 
