@@ -590,6 +590,46 @@ int  paxisim_consensus(paxisim* h, uint64_t* failed, uint64_t* versions, uint64_
  * set when Consensus(k) is false in cluster cluster_lo + i. */
 int  paxisim_consensus_failed(paxisim* h, uint64_t cluster_lo, uint64_t n, uint64_t* key_masks);
 
+/* ---- Message traces of chosen clusters, recorded on the device (DESIGN.md
+ * §3.15).  The trace of replica dst of a traced cluster is what its inbox holds
+ * when its step t begins - what paxisim_read_inbox returns just before step t:
+ * sources 0..N-1 in order, then the client queue (src = N), each in FIFO order,
+ * a multi-record message (P1b, EPaxos) contiguous.  A late worker's first
+ * request is in it (at its start step, behind the requests already queued), and
+ * so are the records a crashed replica's socket.Recv discards and the records
+ * paxisim_inject / paxisim_deliver put there before the step.  Steps after the
+ * one in which the cluster raised PAXISIM_F_POISON are not recorded (the
+ * cluster is frozen, as a Go panic ends the process); the poison step's inboxes
+ * of all replicas are.  Per (traced cluster, replica) the device keeps the count
+ * of records seen and the first records_per_replica of them; later ones are
+ * counted, not kept, and raise no flag.  Replica state, stats, flags, latency
+ * histograms, client histories and Database histories are those of a run
+ * without tracing. */
+#define PAXISIM_TRACE_MAX_CLUSTERS (1u << 16)
+#define PAXISIM_TRACE_MAX_RECORDS  (1u << 20)
+/* {step at which dst received it, source (N = the client), the mailbox record} */
+typedef struct paxisim_trace_record { uint32_t step, src, hdr, ballot, slot, cid; } paxisim_trace_record;
+/* Trace the n_clusters local clusters `clusters` over steps [step_from,
+ * step_to).  Once, before the first step and after paxisim_latency_enable,
+ * whose step kernels it uses (EINVAL otherwise, and for n_clusters == 0 or
+ * above PAXISIM_TRACE_MAX_CLUSTERS, a repeated cluster, records_per_replica
+ * outside [1, PAXISIM_TRACE_MAX_RECORDS] or step_from >= step_to).  ERANGE for
+ * a cluster outside the handle.  ENOMEM: the buffers take n_clusters x replicas
+ * x (records_per_replica x 32 + 4) bytes and 4 bytes per cluster of the handle
+ * (rounded up to 64); a handle that never enables tracing allocates nothing. */
+int  paxisim_trace_enable(paxisim* h, const uint64_t* clusters, uint32_t n_clusters,
+                          uint32_t records_per_replica, uint32_t step_from, uint32_t step_to);
+/* The records one replica of a traced local cluster received, by step, then
+ * source, then FIFO: *n_out is the number kept, of which at most cap are
+ * written to out (may be NULL); *dropped_out (may be NULL) is the count minus
+ * the kept.  EINVAL for a cluster that is not traced, a replica >= N, or when
+ * tracing is not enabled. */
+int  paxisim_trace_read(paxisim* h, uint64_t cluster, uint32_t replica, paxisim_trace_record* out,
+                        uint32_t cap, uint32_t* n_out, uint32_t* dropped_out);
+/* Over every (traced cluster, replica): the records kept and the records
+ * dropped (either may be NULL). */
+int  paxisim_trace_totals(paxisim* h, uint64_t* records, uint64_t* dropped);
+
 /* ---- Multi-GPU: clusters shard by range over handles
  * (paxisim_config.cluster_base = rank * clusters), the simulation itself has
  * no collective, and totals are reduced with RCCL (opened at run time:

@@ -20,6 +20,8 @@ ALL_DST = 0xFF
 LAT_MAX_BINS = 4096          # paxisim_latency_enable: bins is a power of two in [16, LAT_MAX_BINS]
 ALL_WORKERS = 0xFFFFFFFF     # paxisim_latency_get: every worker summed
 MV_MAX = 1 << 16             # paxisim_multiversion_enable: versions_per_key is in [1, MV_MAX]
+TRACE_MAX_CLUSTERS = 1 << 16 # paxisim_trace_enable: n_clusters is in [1, TRACE_MAX_CLUSTERS]
+TRACE_MAX_RECORDS = 1 << 20  # and records_per_replica in [1, TRACE_MAX_RECORDS]
 
 # error codes
 OK, EINVAL, ENOMEM, EDEVICE, EUNSUPP, ERANGE = 0, -1, -2, -3, -4, -5
@@ -183,6 +185,15 @@ class InboxRecord(C.Structure):
         return (self.src, self.hdr, self.ballot, self.slot, self.cid)
 
 
+class TraceRecord(C.Structure):
+    """paxisim_trace_record: one record a traced replica received (paxisim_trace_read)."""
+    _fields_ = [("step", C.c_uint32), ("src", C.c_uint32), ("hdr", C.c_uint32), ("ballot", C.c_uint32),
+                ("slot", C.c_uint32), ("cid", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.step, self.src, self.hdr, self.ballot, self.slot, self.cid)
+
+
 class WorkerState(C.Structure):
     """paxisim_worker_state: a closed-loop worker (benchmark.go:246-275) and its last Reply.Value."""
     _fields_ = [("cid", C.c_uint32), ("issued", C.c_uint32), ("reply_value", C.c_uint32), ("pad", C.c_uint32)]
@@ -236,6 +247,14 @@ MV_PROTOTYPES = {
                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
     "paxisim_consensus": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "paxisim_consensus_failed": [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)],
+}
+
+# C prototypes of the device message trace, likewise
+TRACE_PROTOTYPES = {
+    "paxisim_trace_enable": [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32],
+    "paxisim_trace_read": [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(TraceRecord), C.c_uint32,
+                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "paxisim_trace_totals": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
 }
 
 

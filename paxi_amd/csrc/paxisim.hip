@@ -97,6 +97,10 @@ struct paxisim {
   size_t lat_bytes = 0;
   size_t ch_bytes = 0;             // client-side op history (chist_kernel.h): P.ch_ops and P.ch_cnt
   size_t mv_bytes = 0;             // multi-version Database (mv_kernel.h): P.mv_val and P.mv_cnt
+  // device message trace (trace_kernel.h): P.tr_row, P.tr_rec and P.tr_cnt; tr_rows: clusters traced
+  size_t tr_bytes = 0;
+  uint32_t tr_rows = 0;
+  std::vector<uint32_t> tr_row;    // host copy of P.tr_row
 };
 
 static inline size_t rc_host(const Params& P, uint32_t r, uint64_t c) { return (size_t)r * P.C + c; }
@@ -1010,6 +1014,9 @@ extern "C" int paxisim_destroy(paxisim* h) {
   if (h->P.ch_cnt) (void)hipFree(h->P.ch_cnt);
   if (h->P.mv_val) (void)hipFree(h->P.mv_val);
   if (h->P.mv_cnt) (void)hipFree(h->P.mv_cnt);
+  if (h->P.tr_row) (void)hipFree(const_cast<uint32_t*>(h->P.tr_row));
+  if (h->P.tr_rec) (void)hipFree(h->P.tr_rec);
+  if (h->P.tr_cnt) (void)hipFree(h->P.tr_cnt);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return 0;
@@ -2026,7 +2033,7 @@ extern "C" int paxisim_occupancy(paxisim* h, int* blocks_per_cu, uint32_t* lds_b
 
 extern "C" int paxisim_device_bytes(paxisim* h, uint64_t* bytes) {
   if (!h || !bytes) return fail(PAXISIM_EINVAL, "null argument");
-  *bytes = h->arena_bytes + h->lat_bytes + h->ch_bytes + h->mv_bytes;
+  *bytes = h->arena_bytes + h->lat_bytes + h->ch_bytes + h->mv_bytes + h->tr_bytes;
   return 0;
 }
 
@@ -2510,6 +2517,108 @@ extern "C" int paxisim_consensus_failed(paxisim* h, uint64_t cluster_lo, uint64_
   if (cluster_lo > h->cfg.clusters || n > h->cfg.clusters - cluster_lo) return fail(PAXISIM_ERANGE, "cluster range");
   if (n == 0) return 0;
   return mv_scan(h, cluster_lo, n, nullptr, key_masks);
+}
+
+// ---------------------------------------------------------------------------
+// Message traces of chosen clusters (include/paxisim.h, DESIGN.md §3.15, trace_kernel.h)
+// ---------------------------------------------------------------------------
+extern "C" int paxisim_trace_enable(paxisim* h, const uint64_t* clusters, uint32_t n_clusters,
+                                    uint32_t records_per_replica, uint32_t step_from, uint32_t step_to) {
+  if (!h) return fail(PAXISIM_EINVAL, "null handle");
+  if (h->P.tr_cap) return fail(PAXISIM_EINVAL, "tracing is already enabled");
+  if (h->t) return fail(PAXISIM_EINVAL, "tracing can only be enabled before the first step");
+  if (!h->P.lat_bins)
+    return fail(PAXISIM_EINVAL, "tracing needs the recording step kernels: call paxisim_latency_enable first");
+  if (n_clusters == 0 || n_clusters > PAXISIM_TRACE_MAX_CLUSTERS || !clusters)
+    return fail(PAXISIM_EINVAL, "n_clusters must be in [1, %u]", PAXISIM_TRACE_MAX_CLUSTERS);
+  if (records_per_replica == 0 || records_per_replica > PAXISIM_TRACE_MAX_RECORDS)
+    return fail(PAXISIM_EINVAL, "records_per_replica must be in [1, %u]", PAXISIM_TRACE_MAX_RECORDS);
+  if (step_from >= step_to) return fail(PAXISIM_EINVAL, "empty step window [%u, %u)", step_from, step_to);
+  std::vector<uint32_t> row(h->P.C, TR_NONE);
+  for (uint32_t i = 0; i < n_clusters; i++) {
+    if (clusters[i] >= h->cfg.clusters)
+      return fail(PAXISIM_ERANGE, "traced cluster %llu outside the handle", (unsigned long long)clusters[i]);
+    if (row[clusters[i]] != TR_NONE)
+      return fail(PAXISIM_EINVAL, "cluster %llu is listed twice", (unsigned long long)clusters[i]);
+    row[clusters[i]] = i;
+  }
+  if (const int jrc = enter(h)) return jrc;
+  Params P = h->P;
+  P.tr_cap = records_per_replica;
+  P.tr_from = step_from;
+  P.tr_to = step_to;
+  const size_t rows = (size_t)n_clusters * P.N;
+  const size_t tb = sizeof(uint32_t) * row.size(), cb = sizeof(uint32_t) * rows;
+  const size_t rb = 2 * sizeof(uint4) * rows * records_per_replica;
+  uint32_t* d_row = nullptr;
+  hipError_t e;
+  if ((e = hipMalloc(&d_row, tb)) != hipSuccess || (e = hipMalloc(&P.tr_cnt, cb)) != hipSuccess ||
+      (e = hipMalloc(&P.tr_rec, rb)) != hipSuccess ||
+      (e = hipMemcpyAsync(d_row, row.data(), tb, hipMemcpyHostToDevice, h->stream)) != hipSuccess ||
+      (e = hipMemsetAsync(P.tr_cnt, 0, cb, h->stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(h->stream)) != hipSuccess) {
+    if (d_row) (void)hipFree(d_row);
+    if (P.tr_cnt) (void)hipFree(P.tr_cnt);
+    if (P.tr_rec) (void)hipFree(P.tr_rec);
+    return fail(PAXISIM_ENOMEM, "trace buffers (%zu bytes): %s", tb + cb + rb, hipGetErrorString(e));
+  }
+  P.tr_row = d_row;
+  h->P = P;
+  h->tr_bytes = tb + cb + rb;
+  h->tr_rows = n_clusters;
+  h->tr_row.swap(row);
+  return 0;
+}
+
+// The row is contiguous and found by the cluster id, so the readout is a copy of the count and one
+// of the kept slots.
+extern "C" int paxisim_trace_read(paxisim* h, uint64_t cluster, uint32_t replica, paxisim_trace_record* out,
+                                  uint32_t cap, uint32_t* n_out, uint32_t* dropped_out) {
+  if (!h || !n_out) return fail(PAXISIM_EINVAL, "null argument");
+  if (!h->P.tr_cap) return fail(PAXISIM_EINVAL, "tracing is not enabled");
+  if (cluster >= h->cfg.clusters || h->tr_row[cluster] == TR_NONE)
+    return fail(PAXISIM_EINVAL, "cluster %llu is not traced", (unsigned long long)cluster);
+  if (replica >= h->P.N) return fail(PAXISIM_EINVAL, "no replica %u", replica);
+  if (const int jrc = enter(h)) return jrc;
+  if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
+  const Params& P = h->P;
+  const size_t ri = trace_row(P, h->tr_row[cluster], replica);
+  uint32_t n = 0;
+  HIPCHK(hipMemcpyAsync(&n, &P.tr_cnt[ri], sizeof n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const uint32_t kept = std::min(n, P.tr_cap), take = out ? std::min(kept, cap) : 0u;
+  if (take) {
+    std::vector<uint4> tmp(2 * (size_t)take);
+    HIPCHK(hipMemcpyAsync(tmp.data(), &P.tr_rec[ri * P.tr_cap * 2], tmp.size() * sizeof(uint4), hipMemcpyDeviceToHost,
+                          h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (uint32_t k = 0; k < take; k++) {
+      const uint4 &a = tmp[2 * (size_t)k], &m = tmp[2 * (size_t)k + 1];
+      out[k] = paxisim_trace_record{a.x, a.y, m.x, m.y, m.z, m.w};
+    }
+  }
+  *n_out = kept;
+  if (dropped_out) *dropped_out = n - kept;
+  return 0;
+}
+
+extern "C" int paxisim_trace_totals(paxisim* h, uint64_t* records, uint64_t* dropped) {
+  if (!h) return fail(PAXISIM_EINVAL, "null handle");
+  if (!h->P.tr_cap) return fail(PAXISIM_EINVAL, "tracing is not enabled");
+  if (const int jrc = enter(h)) return jrc;
+  if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
+  const Params& P = h->P;
+  std::vector<uint32_t> cnt((size_t)h->tr_rows * P.N);
+  HIPCHK(hipMemcpyAsync(cnt.data(), P.tr_cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  uint64_t kept = 0, lost = 0;
+  for (const uint32_t n : cnt) {
+    kept += std::min(n, P.tr_cap);
+    lost += n - std::min(n, P.tr_cap);
+  }
+  if (records) *records = kept;
+  if (dropped) *dropped = lost;
+  return 0;
 }
 
 // ---------------------------------------------------------------------------

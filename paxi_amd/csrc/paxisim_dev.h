@@ -246,6 +246,13 @@ struct Params {
   uint32_t mv_cap;               // values kept per (key, replica, cluster)
   uint32_t* mv_val;              // [K][N][C][mv_cap] the first mv_cap values put (command ids)
   uint32_t* mv_cnt;              // [K][N][C] values ever put (counts on past mv_cap)
+  // device message trace (trace_kernel.h); off while tr_cap == 0.  tr_row is indexed
+  // by the local cluster id, as the client history is
+  uint32_t tr_cap;               // records kept per (traced cluster, replica)
+  uint32_t tr_from, tr_to;       // steps [tr_from, tr_to) are recorded
+  const uint32_t* tr_row;        // [C] cluster -> trace row, TR_NONE = not traced
+  uint4* tr_rec;                 // [rows][N][tr_cap][2] {step, src, 0, 0}, the mailbox record
+  uint32_t* tr_cnt;              // [rows][N] records seen (counts on past tr_cap)
 };
 
 // Persistent scalars of the kpaxos instance (blk, k, r, lane) in the record

@@ -15,6 +15,7 @@
 #include "lat_kernel.h"
 #include "chist_kernel.h"
 #include "mv_kernel.h"
+#include "trace_kernel.h"
 
 namespace pxs {
 
@@ -661,6 +662,9 @@ __device__ __forceinline__ void replica_step(const Params& P, Rep<NT>& x
   if constexpr (!LINK_LATE) link_step();
 
   const uint32_t box0 = (x.b0 * N + x.r) * NS;          // inbox boxes: box0 + src
+  if (PXS_LAT) {   // the recording units only: the inbox as this step finds it (trace_kernel.h)
+    if (P.tr_cap) trace_inbox(P, x.gid - P.cluster_base, x.r, x.t, x.lane, x.l_cnt, x.rec, box0, NS);
+  }
   // per source: records left (rem) and the step's initial count, packed in
   // bytes (c0w), so a source's FIFO position is c0 - rem without a register each
   constexpr uint32_t NCW = (NSMAX + 3u) / 4u;
@@ -1359,6 +1363,9 @@ __device__ __forceinline__ void step_async(const Params& P, Rep<NT>& x, uint64_t
       const ScriptedStep sc = P.nfaults ? scripted_scan<NT>(P, x) : ScriptedStep{0u, 0u, 0ull, false};
       x.crashed = sc.crash;
       box0 = (x.b0 * N + r) * NS;
+      if (PXS_LAT) {   // the inbox as this step finds it (trace_kernel.h)
+        if (P.tr_cap) trace_inbox(P, x.gid - P.cluster_base, x.r, x.t, x.lane, x.l_cnt, x.rec, box0, NS);
+      }
       rem.clear();
 #pragma unroll
       for (uint32_t q = 0; q < NCW; q++) c0w[q] = 0;

@@ -110,6 +110,12 @@ def load_library():
             fn = getattr(L, name)
             fn.restype = C.c_int
             fn.argtypes = args
+    # the device message trace: likewise
+    if hasattr(L, "paxisim_trace_enable"):
+        for name, args in abi.TRACE_PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.restype = C.c_int
+            fn.argtypes = args
     if L.paxisim_abi_version() != abi.ABI_VERSION:
         raise PaxisimError("ABI version mismatch between paxi_amd/abi.py and libpaxisim.so")
     _lib = L
@@ -131,7 +137,8 @@ EXPORTED = ["paxisim_abi_version", "paxisim_build_id", "paxisim_last_error", "pa
             "paxisim_latency_enable", "paxisim_latency_reset", "paxisim_latency_get", "paxisim_latency_stat_of",
             "paxisim_client_history_enable", "paxisim_client_history", "paxisim_client_history_load",
             "paxisim_client_linearizable",
-            "paxisim_multiversion_enable", "paxisim_kv_history", "paxisim_consensus", "paxisim_consensus_failed"]
+            "paxisim_multiversion_enable", "paxisim_kv_history", "paxisim_consensus", "paxisim_consensus_failed",
+            "paxisim_trace_enable", "paxisim_trace_read", "paxisim_trace_totals"]
 
 
 def consensus_of_histories(histories):
@@ -408,6 +415,39 @@ class Simulation:
         """HTTPClient.Consensus(key) of one cluster from the replicas' readouts: (True, None), or
         (False, the first index at which two replicas hold different values)."""
         return consensus_of_histories([self.kv_history(cluster, r, key)[0] for r in range(self.N)])
+
+    # message traces of chosen clusters, recorded on the device (DESIGN.md §3.15)
+    @staticmethod
+    def _trace(name):
+        fn = getattr(load_library(), name, None)
+        if fn is None:
+            raise PaxisimError(f"{LIB_PATH} was built without {name} (device message trace)")
+        return fn
+
+    def trace_enable(self, clusters, records_per_replica, step_from=0, step_to=2**32 - 1):
+        """Record what every replica of the local clusters `clusters` receives at steps [step_from,
+        step_to): the first `records_per_replica` records per (cluster, replica), later ones counted
+        as dropped; once, before the first step and after latency_enable."""
+        clusters = list(clusters)
+        arr = (C.c_uint64 * max(1, len(clusters)))(*clusters)
+        _check(self._trace("paxisim_trace_enable")(self.h, arr, len(clusters), records_per_replica, step_from,
+                                                   step_to))
+
+    def trace_read(self, cluster, replica):
+        """([(step, src, hdr, ballot, slot, cid)] one replica of a traced cluster received, by step,
+        then source, then FIFO; records dropped past records_per_replica)."""
+        fn = self._trace("paxisim_trace_read")
+        n, d = C.c_uint32(), C.c_uint32()
+        _check(fn(self.h, cluster, replica, None, 0, C.byref(n), C.byref(d)))
+        arr = (abi.TraceRecord * max(1, n.value))()
+        _check(fn(self.h, cluster, replica, arr, n.value, C.byref(n), C.byref(d)))
+        return [arr[i].as_tuple() for i in range(n.value)], d.value
+
+    def trace_totals(self):
+        """(records kept, records dropped) over every traced (cluster, replica)."""
+        k, d = C.c_uint64(), C.c_uint64()
+        _check(self._trace("paxisim_trace_totals")(self.h, C.byref(k), C.byref(d)))
+        return k.value, d.value
 
     def close(self):
         if self.h:

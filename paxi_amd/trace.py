@@ -10,6 +10,8 @@ message as a gob stream, one `gob.Encoder` per connection
 - `capture(sim, cluster, steps)` steps a simulation one step at a time and
   records, before each step, every replica's inbox (paxisim_read_inbox): what
   each link delivers, in link (FIFO) order, plus the client's HTTP requests;
+- `from_device(sim, cluster)` gives the same trace from the device recorder
+  (Simulation.trace_enable, DESIGN.md §3.15) of a run stepped in any chunks;
 - `export(trace)` turns each directed link's messages into the bytes a Paxi
   sender's encoder writes on that connection (`gob.Encoder.Encode(&m)` with
   m an `interface{}`, paxi_amd/gob.py) and keeps the client requests, which
@@ -352,6 +354,37 @@ def capture(sim, cluster, steps):
                     out.append((t, src, dst, m))
         sim.step(1)
     return {"N": N, "t0": t0, "steps": steps, "msgs": out}
+
+
+def from_rows(N, rows, t0, steps, truncated=False):
+    """The trace `capture` returns, from the device recorder's rows: rows[dst] is
+    what Simulation.trace_read gives for replica dst, ([(step, src, hdr, ballot, slot, cid)] in
+    step, source and FIFO order, records dropped).  Records of steps outside [t0, t0 + steps) are
+    left out.  A row that dropped records is no whole trace: TraceError, unless truncated=True
+    (the last message of such a row may lack payload records)."""
+    by = {}
+    for dst in range(N):
+        recs, dropped = rows[dst]
+        if dropped and not truncated:
+            raise TraceError(f"replica {dst}: {dropped} records dropped past the {len(recs)} kept "
+                             "(raise records_per_replica, or pass truncated=True)")
+        for (t, src, hdr, ballot, slot, cid) in recs:
+            if t0 <= t < t0 + steps:
+                by.setdefault((t, dst, src), []).append((src, hdr, ballot, slot, cid))
+    out = []
+    for (t, dst, src) in sorted(by):
+        for m in _split(by[(t, dst, src)]):
+            out.append((t, src, dst, m))
+    return {"N": N, "t0": t0, "steps": steps, "msgs": out}
+
+
+def from_device(sim, cluster, t0=0, steps=None, truncated=False):
+    """The trace of a cluster recorded on the device (Simulation.trace_enable) over steps [t0,
+    t0 + steps), by default up to the simulation's current step: what `capture` would have
+    returned, without its per-step readouts."""
+    if steps is None:
+        steps = sim.stats().steps - t0
+    return from_rows(sim.N, [sim.trace_read(cluster, r) for r in range(sim.N)], t0, steps, truncated)
 
 
 def export(sim, cluster, trace, outdir=None):

@@ -1,6 +1,6 @@
 """Capture a cluster's message trace as Paxi gob streams, or replay one.
 
-    python tools/trace_cli.py capture --config 2 --cluster 3 --steps 300 [--clusters 64] --out DIR
+    python tools/trace_cli.py capture --config 2 --cluster 3 --steps 300 [--clusters 64] [--device] --out DIR
     python tools/trace_cli.py replay DIR
 
 `capture` runs a BASELINE config (bench.py's workloads) on the GPU, records the
@@ -8,6 +8,9 @@ chosen cluster's inbox step by step and writes DIR/<src>-<dst>.gob (the bytes a
 Paxi sender's gob.Encoder writes on that TCP connection, transport.go:108),
 DIR/schedule.json (delivery steps, the client's HTTP requests), and
 DIR/run.json (the configuration and the captured replicas' final state).
+With --device the cluster is traced by the device recorder:
+one step(n) call instead of one step and N inbox readouts per step, and the
+same files.
 `replay` rebuilds that configuration for the one cluster, decodes the streams
 (paxi_amd/trace.py) and delivers them into a run whose links are all dropped,
 then compares each replica's final state with the captured one.
@@ -64,7 +67,13 @@ def capture(args, backend=None):
     ns = argparse.Namespace(window=d["window"], mbox=d["mbox"], history=512, kv=1, crash_step=args.crash_step)
     cfg, wl, fp, faults, desc = bench.workload(args.config, args.clusters, 0, 0, ns)
     sim = backend(cfg, wl, fp, faults)
-    tr = trace.capture(sim, args.cluster, args.steps)
+    if getattr(args, "device", False):
+        sim.latency_enable(16)                       # the recording step kernels
+        sim.trace_enable([args.cluster], getattr(args, "records", None) or 64 * args.steps)
+        sim.step(args.steps)
+        tr = trace.from_device(sim, args.cluster, 0, args.steps)
+    else:
+        tr = trace.capture(sim, args.cluster, args.steps)
     streams, sched = trace.export(sim, args.cluster, tr, outdir=args.out)
     state = [list(s.as_tuple()[:8]) + [list(s.as_tuple()[8])] + list(s.as_tuple()[9:])
              for s in sim.read_state(args.cluster, 1)]
@@ -109,6 +118,9 @@ def main(argv=None):
     c.add_argument("--clusters", type=int, default=64)
     c.add_argument("--steps", type=int, default=300)
     c.add_argument("--crash-step", type=int, default=100)
+    c.add_argument("--device", action="store_true", help="trace with the device recorder, in one step(n)")
+    c.add_argument("--records", type=int, default=0,
+                   help="--device: records kept per replica (default 64 per step)")
     c.add_argument("--out", required=True)
     r = sub.add_parser("replay")
     r.add_argument("dir")
