@@ -406,7 +406,9 @@ int  paxisim_read_instances(paxisim* h, uint64_t cluster_lo, uint64_t n,
                             paxisim_instance_state* out);
 
 /* Log entries of slots [slot_lo, slot_lo + n) of one Paxos instance (replica;
- * WPaxos: the kpaxos of `key`) of local cluster `cluster`. */
+ * WPaxos: the kpaxos of `key`) of local cluster `cluster`.  EPaxos and ABD
+ * keep no Paxos log: PAXISIM_EUNSUPP, before anything is launched (EPaxos
+ * exposes its per-owner logs through paxisim_read_instances). */
 int  paxisim_read_log(paxisim* h, uint64_t cluster, uint32_t replica, uint32_t key, int32_t slot_lo,
                       uint32_t n, paxisim_log_entry* out);
 

@@ -1937,6 +1937,8 @@ int oracle_read_log(oracle_sim* s, uint64_t cl, uint32_t r, uint32_t key, int32_
   const inst_t* p;
   uint32_t i;
   if (!s || !out || cl >= s->C || r >= s->N || key >= s->NK) return fail(PAXISIM_EINVAL, "bad argument");
+  if (s->cfg.protocol == PAXISIM_EPAXOS || s->cfg.protocol == PAXISIM_ABD)
+    return fail(PAXISIM_EUNSUPP, "read_log: the protocol keeps no Paxos log");
   p = &s->cl[cl].rep[r].inst[key];
   for (i = 0; i < n; i++) {
     const int32_t sl = lo + (int32_t)i;

@@ -1924,6 +1924,8 @@ extern "C" int paxisim_deliver(paxisim* h, uint64_t cluster, uint32_t replica, u
 extern "C" int paxisim_read_log(paxisim* h, uint64_t cluster, uint32_t replica, uint32_t key, int32_t slot_lo,
                                 uint32_t n, paxisim_log_entry* out) {
   if (!h || !out) return fail(PAXISIM_EINVAL, "null argument");
+  if (h->cfg.protocol == PAXISIM_EPAXOS || h->cfg.protocol == PAXISIM_ABD)   // no Paxos window in the image
+    return fail(PAXISIM_EUNSUPP, "read_log: the protocol keeps no Paxos log (EPaxos: read_instances)");
   if (cluster >= h->cfg.clusters || replica >= h->P.N || key >= h->P.NK) return fail(PAXISIM_ERANGE, "bad entry");
   if (n == 0) return 0;
   if (const int jrc = enter(h)) return jrc;

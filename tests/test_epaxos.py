@@ -82,6 +82,18 @@ def test_nil_gap_reexecutes(seed):
     assert o.stats().dropped == 2
 
 
+@pytest.mark.parametrize("proto", [abi.EPAXOS, abi.ABD])
+def test_read_log_is_refused(proto):
+    """EPaxos and ABD keep no Paxos log: read_log is PAXISIM_EUNSUPP (the device side is in
+    tests/test_epaxos_edges_gpu.py)."""
+    o = ol.OracleSim(abi.make_config(protocol=proto, npz=[3], clusters=2, keys=2, mbox_cap=16, max_delay=1),
+                     abi.make_workload(outstanding=1))
+    o.step(5)
+    with pytest.raises(RuntimeError, match=r"oracle error -4:"):
+        o.read_log(0, 0, 0, 4)
+    o.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("npz,keys,faults", [((3,), 1, False), ((5,), 4, True), ((2, 2, 3), 8, True)])
 def test_gpu_parity(npz, keys, faults):
