@@ -8,7 +8,6 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
-#include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -24,19 +23,13 @@
 #include "lin_kernel.h"
 #include "paxisim_dev.h"
 #include "sim_core.h"
+#include "create_plan.h"
 #include "pool_plan.h"
 #include "step_ops.h"
 
 using namespace pxs;
 
-static thread_local char g_err[512];
-static int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
+static_assert(PLAN_EP_NMAX == EP_NMAX, "create_plan.h check_config: the EPaxos replica limit");
 #define HIPCHK(expr)                                                                  \
   do {                                                                                \
     hipError_t e_ = (expr);                                                           \
@@ -807,130 +800,6 @@ __global__ void replay_kernel(Params P, uint64_t s0, uint64_t s1, uint32_t tnow)
 // ---------------------------------------------------------------------------
 // C-ABI
 // ---------------------------------------------------------------------------
-static Image proto_image(uint32_t protocol, uint32_t N, uint32_t W, uint32_t K, uint32_t WK, uint32_t D,
-                         uint32_t wlds, bool packed) {
-  if (protocol == PAXISIM_ABD) {
-    const uint32_t kv = N * K * LANES * 4u;
-    return image_layout(kv, kv, N * abd_ow(WK) * ABD_OPF * LANES * 4u, N, WK, D);
-  }
-  if (protocol == PAXISIM_WPAXOS)   // instance scalars in the image (wlds), or all in HBM
-    return image_layout(wlds ? K * N * WP_WORDS * LANES * 4u : 0u, 0, 0, N, WK, D);
-  if (protocol == PAXISIM_EPAXOS) return image_layout(0, 0, 0, N, WK, D);   // state in HBM
-  // Multi-Paxos: the window's three planes, or none - the packed serial units keep their entries
-  // outside the image (Params::plog)
-  const uint32_t logb = packed ? 0u : N * W * LANES * 4u;
-  return image_layout(logb, logb, logb, N, WK, D);
-}
-
-// The serial kernel (one wave per tile plays every replica, sim_core.h
-// sim_serial) for the protocols that have it; PAXISIM_SERIAL=0/1 overrides
-// (A/B).  Any other value is refused (serial_env_ok), so an A/B arm cannot
-// silently measure the default kernel.
-static bool serial_env_ok() {
-  const char* e = getenv("PAXISIM_SERIAL");
-  return !e || !strcmp(e, "0") || !strcmp(e, "1");
-}
-static bool serial_for(uint32_t protocol) {
-  const char* e = getenv("PAXISIM_SERIAL");
-  (void)protocol;
-  return !e || strcmp(e, "0") != 0;
-}
-
-// The workload's key space (paxisim.h): ORDER / UNIFORM / CONFLICT range over
-// key_space indices; CONFLICT's literal key 0 is its own index when key_min != 0.
-static uint32_t key_space_of(const paxisim_config* cfg, const paxisim_workload* wl) {
-  const uint32_t keys = cfg->keys ? cfg->keys : 1u;
-  return wl->key_space ? wl->key_space : keys;
-}
-static int check_keys(const paxisim_config* cfg, const paxisim_workload* wl) {
-  const uint32_t keys = cfg->keys ? cfg->keys : 1u;
-  const uint32_t ks = key_space_of(cfg, wl);
-  if (ks > keys) return fail(PAXISIM_EINVAL, "key_space %u exceeds keys %u", ks, keys);
-  if (wl->distribution == PAXISIM_DIST_CONFLICT && wl->key_min && ks >= keys)
-    return fail(PAXISIM_EINVAL, "conflict with key_min != 0 needs key_space < keys (literal key 0 has its own index)");
-  if (wl->distribution == PAXISIM_DIST_TABLE) {
-    for (uint32_t k = 1; k + 1u < keys; k++)
-      if (wl->key_cdf[k] < wl->key_cdf[k - 1]) return fail(PAXISIM_EINVAL, "key_cdf must be non-decreasing");
-    if (wl->key_tail && keys >= 2 && wl->key_tail < wl->key_cdf[keys - 2])
-      return fail(PAXISIM_EINVAL, "key_tail below the last key_cdf threshold");
-  } else if (wl->key_tail) {
-    return fail(PAXISIM_EINVAL, "key_tail needs a table distribution");
-  }
-  if (wl->move_every) {
-    if (wl->distribution != PAXISIM_DIST_TABLE) return fail(PAXISIM_EINVAL, "move_every needs a table distribution");
-    if (!wl->move_cdf || wl->move_tables < 1 || wl->move_loop >= wl->move_tables)
-      return fail(PAXISIM_EINVAL, "move_cdf / move_tables / move_loop");
-    for (uint32_t e = 0; e < wl->move_tables; e++)
-      for (uint32_t k = 1; k + 1u < keys; k++)
-        if (wl->move_cdf[e * PAXISIM_MAX_KEYS + k] < wl->move_cdf[e * PAXISIM_MAX_KEYS + k - 1])
-          return fail(PAXISIM_EINVAL, "move_cdf table %u must be non-decreasing", e);
-  }
-  return 0;
-}
-
-static int check_config(const paxisim_config* cfg, const paxisim_workload* wl, const paxisim_fault_process* fp,
-                        uint32_t* N_out) {
-  uint32_t N = 0;
-  if (cfg->protocol > PAXISIM_EPAXOS || cfg->protocol == PAXISIM_M2PAXOS || cfg->protocol == PAXISIM_KPAXOS)
-    return fail(PAXISIM_EUNSUPP, "protocol %u not built", cfg->protocol);
-  if (cfg->protocol == PAXISIM_EPAXOS && (cfg->keys < 1 || cfg->keys > 32))
-    return fail(PAXISIM_EINVAL, "EPaxos keys must be in [1,32]");
-  if (cfg->protocol == PAXISIM_ABD && (cfg->keys < 1 || cfg->keys > 64)) return fail(PAXISIM_EINVAL, "keys");
-  if (cfg->protocol == PAXISIM_WPAXOS && (cfg->keys < 1 || cfg->keys > 32))
-    return fail(PAXISIM_EINVAL, "WPaxos keys must be in [1,32]");
-  if (cfg->policy_threshold > 255) return fail(PAXISIM_EINVAL, "policy_threshold");
-  if (cfg->policy > PAXISIM_POLICY_EMA) return fail(PAXISIM_EINVAL, "policy %u", cfg->policy);
-  if (cfg->policy == PAXISIM_POLICY_MAJORITY && cfg->policy_interval < 1) return fail(PAXISIM_EINVAL, "policy_interval");
-  if (cfg->policy == PAXISIM_POLICY_EMA && !(cfg->policy_alpha > 0.0 && cfg->policy_alpha <= 1.0))
-    return fail(PAXISIM_EINVAL, "policy_alpha must be in (0, 1]");
-  if (cfg->n_zones < 1 || cfg->n_zones > PAXISIM_MAX_ZONES) return fail(PAXISIM_EINVAL, "n_zones");
-  for (uint32_t z = 0; z < cfg->n_zones; z++) {
-    if (cfg->npz[z] < 1) return fail(PAXISIM_EINVAL, "npz[%u] must be >= 1", z);
-    N += cfg->npz[z];
-  }
-  if (N < 1 || N > PAXISIM_MAX_N) return fail(PAXISIM_EINVAL, "N=%u out of range", N);
-  if (cfg->protocol == PAXISIM_ABD && N > 15) return fail(PAXISIM_EINVAL, "ABD supports N <= 15");
-  if (cfg->protocol == PAXISIM_EPAXOS && N > EP_NMAX) return fail(PAXISIM_EINVAL, "EPaxos supports N <= %u", EP_NMAX);
-  if (cfg->window < 8 || cfg->window > PAXISIM_MAX_WINDOW || (cfg->window & (cfg->window - 1)))
-    return fail(PAXISIM_EINVAL, "window must be a power of 2 in [8,64]");
-  if (cfg->mbox_cap < 2 || cfg->mbox_cap > PAXISIM_MAX_MBOX) return fail(PAXISIM_EINVAL, "mbox_cap");
-  if (cfg->max_delay > PAXISIM_MAX_DELAY) return fail(PAXISIM_EINVAL, "max_delay");
-  if (cfg->q1 > PAXISIM_Q_FGRID_Q2 || cfg->q2 > PAXISIM_Q_FGRID_Q2) return fail(PAXISIM_EINVAL, "quorum kind");
-  if (cfg->clusters < 1) return fail(PAXISIM_EINVAL, "clusters");
-  if (cfg->agree_ring > 65536) return fail(PAXISIM_EINVAL, "agree_ring > 65536");
-  if (wl->outstanding < 1 || wl->outstanding > PAXISIM_MAX_WORKERS) return fail(PAXISIM_EINVAL, "outstanding");
-  if (wl->outstanding > cfg->mbox_cap) return fail(PAXISIM_EINVAL, "outstanding exceeds mbox_cap");
-  if (wl->distribution > PAXISIM_DIST_TABLE) return fail(PAXISIM_EINVAL, "distribution %u", wl->distribution);
-  if (wl->distribution == PAXISIM_DIST_CONFLICT && wl->conflicts > 100) return fail(PAXISIM_EINVAL, "conflicts > 100");
-  if (int rc = check_keys(cfg, wl)) return rc;
-  if (!serial_env_ok()) return fail(PAXISIM_EINVAL, "PAXISIM_SERIAL must be 0 or 1");
-  for (uint32_t w = 0; w < wl->outstanding; w++)
-    if (wl->target[w] >= N) return fail(PAXISIM_EINVAL, "target[%u]", w);
-  if (fp->slow_ppm && (fp->slow_min > fp->slow_max || fp->slow_max > cfg->max_delay))
-    return fail(PAXISIM_EINVAL, "slow delay range exceeds max_delay");
-  const bool serial = serial_for(cfg->protocol);
-  const Image img = proto_image(cfg->protocol, N, cfg->window, cfg->keys, wl->outstanding, cfg->max_delay + 2u, 0,
-                                serial && cfg->protocol == PAXISIM_PAXOS && paxos_packed(N));
-  // the serial kernel keeps only the image's tail (client tables on) in LDS;
-  // either kernel adds the agreement-ring arrival counts after the image
-  const bool ring = cfg->protocol != PAXISIM_ABD && cfg->protocol != PAXISIM_EPAXOS;
-  const uint32_t agn = ring ? (2u * N * LANES + 15u) & ~15u : 0u;
-  const uint32_t need = (serial ? img.bytes - img.off_wcur : img.bytes) + agn;
-  if (need > LDS_MAX)
-    return fail(PAXISIM_EUNSUPP, "%s %u B exceeds LDS (%u B): reduce %smax_delay/replicas",
-                serial ? "serial LDS (image tail and arrival counts)" : "workgroup image and arrival counts", need,
-                LDS_MAX, serial ? "" : "window/");
-  *N_out = N;
-  return 0;
-}
-
-template <typename T>
-static T* carve(char*& p, size_t count) {
-  T* out = reinterpret_cast<T*>(p);
-  p += (count * sizeof(T) + 255) & ~size_t(255);
-  return out;
-}
-
 static int pipe_check(paxisim* h);
 
 // Every entry point but paxisim_step works on the handle's stream.  With two pools it first makes
@@ -1063,30 +932,40 @@ static StepOps lat_step_ops_for(uint32_t protocol, uint32_t N, bool wlds, bool s
 
 static hipError_t ensure_lds(paxisim* h);
 
+static size_t count_blocks(size_t slots) { return (slots + CB - 1) / CB; }
+// a pool's pipeline words: the header, then the chunks done per tile (the XCD probe writes 64 words there)
+static size_t pipe_words(size_t C) { return 16 + (C / LANES > 64 ? C / LANES : 64); }
+// a pool's compaction and phase-binning scratch, for a region of nblk counting blocks
+static hipError_t pool_scratch(Pool& pl, size_t C, size_t nblk) {
+  hipError_t e = hipMalloc(&pl.d_cmp, sizeof(uint32_t) * (CM_SUMS + nblk));
+  if (e == hipSuccess) e = hipMalloc(&pl.d_pairs, sizeof(uint32_t) * 2 * (C / 2 + LANES));
+  if (e == hipSuccess) e = hipMalloc(&pl.d_ph, sizeof(uint32_t) * (PH_SUMS + 2 * nblk));
+  return e;
+}
+
+// the wave slots the handle's step kernel keeps resident on the current device (0: not known)
+static uint32_t resident_slots(paxisim* h) {
+  int dev = 0, cus = 0, per = 0;
+  const bool ok = ensure_lds(h) == hipSuccess && hipGetDevice(&dev) == hipSuccess &&
+                  hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+                  h->ops.occupancy(h->P, &per) == hipSuccess && cus > 0 && per > 0;
+  (void)hipGetLastError();
+  return ok ? (uint32_t)(cus * per) : 0u;
+}
+
 // Cluster pools.  Two pools only for a handle that compacts and runs pipelined
 // serial launches (Multi-Paxos); every other handle runs one.  PAXISIM_POOLS=1|2 decides; without it a
 // 5-replica handle takes two when its tiles are at least four times the resident wave slots (config 2:
 // 16,384 tiles against 2,048 slots, +2.7% in both mirrored pairs; no test-size handle).  The 9-replica
 // unit is left out by rule: config 4 measured -0.7% with two pools.  The split is a multiple of 8 tiles
 // as near the middle as that allows (pool_plan.h); if it leaves a region empty the handle runs one pool.
-static int pools_setup(paxisim* h) {
+static int pools_setup(paxisim* h, const Knobs& kn) {
   const Params& P = h->P;
-  const char* pe = getenv("PAXISIM_POOLS");
-  if (pe && strcmp(pe, "1") && strcmp(pe, "2")) return fail(PAXISIM_EINVAL, "PAXISIM_POOLS must be 1 or 2");
-  const bool can = P.compact && h->pipe_max > 1 && h->ops.serial && h->ops.launch_pipe;
+  if (kn.pools < 0) return fail(PAXISIM_EINVAL, "PAXISIM_POOLS must be 1 or 2");
+  const bool can = P.compact && h->pipe_max > 1;   // pipelined (plan_schedule)
   const uint32_t tiles = (uint32_t)(P.C / LANES);
-  uint32_t want = 1;
-  if (pe) {
-    want = (uint32_t)atoi(pe);
-  } else if (can && P.N == 5) {
-    int dev = 0, cus = 0, per = 0;
-    if (ensure_lds(h) == hipSuccess && hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-        h->ops.occupancy(P, &per) == hipSuccess && cus > 0 && per > 0 && tiles >= 4u * (uint32_t)(cus * per))
-      want = 2;
-    (void)hipGetLastError();
-  }
-  const uint32_t split = can && want > 1 ? pool_split_tile(tiles, h->cfg.clusters) : 0u;
+  const uint32_t slots = pool_want_asks_slots(kn.pools, can, P.N) ? resident_slots(h) : 0u;
+  const uint32_t split = pool_want(kn.pools, can, P.N, tiles, slots) > 1 ? pool_split_tile(tiles, h->cfg.clusters) : 0u;
   if (!split) return 0;
   Pool& a = h->pool[0];
   Pool& b = h->pool[1];
@@ -1094,8 +973,6 @@ static int pools_setup(paxisim* h) {
   a.end = b.base = split * LANES;
   b.end = (uint32_t)C;
   b.last_cmp = pool_first_cmp(1, h->S);
-  const size_t nblk = (C - b.base + CB - 1) / CB;
-  const size_t nq = 16 + (C / LANES > 64 ? C / LANES : 64);
   hipError_t e;
   a.stream = nullptr;
   h->npools = 2;   // from here on paxisim_destroy frees what was made
@@ -1104,13 +981,104 @@ static int pools_setup(paxisim* h) {
       (e = hipEventCreateWithFlags(&a.ev, hipEventDisableTiming)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&b.ev, hipEventDisableTiming)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming)) != hipSuccess ||
-      (e = hipMalloc(&b.d_cmp, sizeof(uint32_t) * (CM_SUMS + nblk))) != hipSuccess ||
-      (e = hipMalloc(&b.d_pairs, sizeof(uint32_t) * 2 * (C / 2 + LANES))) != hipSuccess ||
-      (e = hipMalloc(&b.d_ph, sizeof(uint32_t) * (PH_SUMS + 2 * nblk))) != hipSuccess ||
-      (e = hipMalloc(&b.d_pipe, sizeof(uint32_t) * nq)) != hipSuccess ||
+      (e = pool_scratch(b, C, count_blocks(C - b.base))) != hipSuccess ||
+      (e = hipMalloc(&b.d_pipe, sizeof(uint32_t) * pipe_words(C))) != hipSuccess ||
       // the pipeline words of pool 0 with their spin limit; the error word starts clear
       (e = hipMemcpyAsync(b.d_pipe, a.d_pipe, sizeof(uint32_t) * 16, hipMemcpyDeviceToDevice, h->stream)) != hipSuccess)
     return fail(PAXISIM_EDEVICE, "cluster pool setup failed: %s", hipGetErrorString(e));
+  return 0;
+}
+
+// Pipelined launches (serial kernels): pool 0's pipeline words with the poll limit of a chunk wait
+// (sim_core.h pipe_item), and the XCD probe - workgroups must go round robin over the 8 XCDs, in any
+// rotation, or the handle does not pipeline (*probe_ok).
+static int pipe_setup(paxisim* h, const Knobs& kn, bool* probe_ok) {
+  uint32_t*& q = h->pool[0].d_pipe;
+  uint32_t xcc[64] = {0};
+  const uint32_t spin = kn.has_pipe_spin ? kn.pipe_spin : PXS_PIPE_SPIN_DEFAULT;
+  hipError_t e;
+  if ((e = hipMalloc(&q, sizeof(uint32_t) * pipe_words(h->P.C))) != hipSuccess ||
+      (e = hipMemsetAsync(q, 0, sizeof(uint32_t) * 16, h->stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(q + 9, &spin, sizeof spin, hipMemcpyHostToDevice, h->stream)) != hipSuccess)
+    return fail(PAXISIM_EDEVICE, "pipelined launch setup failed: %s", hipGetErrorString(e));
+  xcc_probe<<<64, 64, 0, h->stream>>>(q + 16);
+  if ((e = hipGetLastError()) != hipSuccess ||
+      (e = hipMemcpyAsync(xcc, q + 16, sizeof xcc, hipMemcpyDeviceToHost, h->stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(h->stream)) != hipSuccess)
+    return fail(PAXISIM_EDEVICE, "XCD probe failed: %s", hipGetErrorString(e));
+  for (uint32_t b = 0; b < 64; b++)
+    if ((xcc[b] & 7u) != ((xcc[0] + b) & 7u) || xcc[b] > 7u) *probe_ok = false;
+  return 0;
+}
+
+// Everything of paxisim_create after `new`: the plan (create_plan.h) between the device calls it
+// needs.  On a failure the caller destroys the partly built handle.
+static int create_on_device(paxisim* h, const Knobs& kn, uint32_t variant, uint32_t N) {
+  const paxisim_config* cfg = &h->cfg;
+  Params& P = h->P;
+  fill_params(P, h->zone_of, h->node_of, h->S, cfg, &h->wl, &h->fp, variant, N, kn);
+  h->ops = step_ops_for(P.protocol, N, P.wlds != 0, kn.serial);
+  KernelFacts kf;
+  if (h->ops.attrs(&kf.vgprs, &kf.max_threads) != hipSuccess) kf.vgprs = 0;
+  kf.staged = h->ops.staged;
+  kf.serial = h->ops.serial;
+  kf.has_pipe = h->ops.launch_pipe != nullptr;
+  if (const int rc = plan_lds(P, kn, kf)) return rc;
+
+  // the arena: sized, placed, bound.  PAXISIM_ARENA_PAD_MB reserves that much device memory first
+  // and frees it once the arena is placed; PAXISIM_ARENA_CONTIG=1 asks for physically contiguous
+  // memory.  Placement only.
+  const ArenaSize sz = carve_arena(P, cfg->policy, nullptr, false);
+  void* pad = nullptr;
+  if (kn.arena_pad_mb > 0) (void)hipMalloc(&pad, (size_t)kn.arena_pad_mb << 20);
+  hipError_t e = kn.arena_contig ? hipExtMallocWithFlags(&h->arena, sz.total, hipDeviceMallocContiguous)
+                                 : hipMalloc(&h->arena, sz.total);
+  if (pad) (void)hipFree(pad);
+  if (e != hipSuccess) return fail(PAXISIM_ENOMEM, "hipMalloc(%zu bytes) failed: %s", sz.total, hipGetErrorString(e));
+  h->arena_bytes = sz.total;
+  carve_arena(P, cfg->policy, (char*)h->arena, true);
+
+  const size_t C = P.C;
+  if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess ||
+      (e = hipMalloc(&h->d_scratch, sizeof(uint64_t) * 64)) != hipSuccess ||
+      (e = pool_scratch(h->pool[0], C, count_blocks(cfg->clusters))) != hipSuccess ||
+      (e = hipMalloc(&h->d_faults, sizeof(DevFault) * PAXISIM_MAX_FAULTS)) != hipSuccess ||
+      (e = hipMemsetAsync(h->arena, 0, sz.zero_bytes, h->stream)) != hipSuccess)
+    return fail(PAXISIM_EDEVICE, "device setup failed: %s", hipGetErrorString(e));
+  if (P.move_every) {   // the moving-Mu tables (the caller's buffer is not kept)
+    const size_t mb = (size_t)P.move_tables * PAXISIM_MAX_KEYS * sizeof(uint32_t);
+    if ((e = hipMalloc(&h->d_move, mb)) != hipSuccess ||
+        (e = hipMemcpy(h->d_move, h->wl.move_cdf, mb, hipMemcpyHostToDevice)) != hipSuccess)
+      return fail(PAXISIM_EDEVICE, "move_cdf upload failed: %s", hipGetErrorString(e));
+    P.move_cdf = h->d_move;
+  }
+  h->wl.move_cdf = nullptr;
+  P.faults = h->d_faults;
+  P.bound = h->pool[0].d_cmp;
+  h->pool[0].stream = h->stream;
+  h->pool[0].end = (uint32_t)C;
+
+  bool probe_ok = true;
+  if (plan_pipe(kn, kf) > 1)
+    if (const int rc = pipe_setup(h, kn, &probe_ok)) return rc;
+  const Schedule sc = plan_schedule(P, kn, kf, h->S, probe_ok);
+  P.compact = sc.compact;
+  h->late_until = sc.late_until;
+  h->pipe_max = sc.pipe_max;
+  h->cmp_every = sc.cmp_every;
+  h->pipe_slots = kn.pipe_slots;
+  if (const int rc = pools_setup(h, kn)) return rc;
+
+  // every pool's bound: the clusters of its region
+  uint32_t b0 = (uint32_t)cfg->clusters;
+  h->bound_host = b0;
+  for (uint32_t p = h->npools; p-- > 1 && e == hipSuccess;)
+    e = hipMemcpyAsync(h->pool[p].d_cmp, &b0, sizeof b0, hipMemcpyHostToDevice, h->stream);
+  if (h->npools > 1) b0 = h->pool[0].end;
+  if (e == hipSuccess) e = hipMemcpyAsync(h->pool[0].d_cmp, &b0, sizeof b0, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) init_kernel<<<(unsigned)((C + 255) / 256), 256, 0, h->stream>>>(P);
+  if (e != hipSuccess || (e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(h->stream)) != hipSuccess)
+    return fail(PAXISIM_EDEVICE, "init kernel failed: %s", hipGetErrorString(e));
   return 0;
 }
 
@@ -1126,9 +1094,9 @@ extern "C" int paxisim_create(const paxisim_config* cfg, const paxisim_workload*
   paxisim_fault_process nofp;
   memset(&nofp, 0, sizeof nofp);
   if (!fp) fp = &nofp;
+  const Knobs kn = knobs_from_env();
   uint32_t N = 0;
-  int rc0 = check_config(cfg, wl, fp, &N);
-  if (rc0) return rc0;
+  if (const int rc = check_config(cfg, wl, fp, kn, &N)) return rc;
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (cfg->device < 0 || cfg->device >= ndev) return fail(PAXISIM_EDEVICE, "device %d not present (%d visible)", cfg->device, ndev);
@@ -1139,351 +1107,9 @@ extern "C" int paxisim_create(const paxisim_config* cfg, const paxisim_workload*
   h->cfg = *cfg;
   h->wl = *wl;
   h->fp = *fp;
-  h->S = cfg->steps_per_launch ? cfg->steps_per_launch : 32;
-  {   // per-type delivered counts are 16-bit in the kernel: at most NS*M messages per replica-step
-    const uint32_t smax = 65535u / ((N + 1u) * cfg->mbox_cap);
-    if (h->S > smax) h->S = smax;
-  }
-  Params& P = h->P;
-  memset(&P, 0, sizeof P);
-  P.protocol = cfg->protocol;
-  P.N = N;
-  P.Z = cfg->n_zones;
-  P.keys = cfg->keys ? cfg->keys : 1;
-  P.write_ppm = wl->write_ppm;
-  P.locality_ppm = wl->locality_ppm;
-  P.dist = wl->distribution;
-  P.conflicts = wl->conflicts;
-  memcpy(P.key_cdf, wl->key_cdf, sizeof P.key_cdf);
-  P.NK = cfg->protocol == PAXISIM_WPAXOS ? P.keys : 1u;
-  P.NI = P.NK * N;
-  P.adaptive = cfg->adaptive;
-  P.policy_thr = cfg->policy_threshold;
-  P.policy = cfg->policy;
-  P.policy_interval = cfg->policy_interval;
-  P.policy_alpha = cfg->policy_alpha;
-  P.H = cfg->protocol == PAXISIM_ABD ? cfg->history : 0;
-  P.AR = (cfg->protocol == PAXISIM_ABD || cfg->protocol == PAXISIM_EPAXOS) ? 0u
-         : cfg->agree_ring ? cfg->agree_ring : (cfg->protocol == PAXISIM_WPAXOS ? 128u : 1024u);
-  P.OW = abd_ow(wl->outstanding);
-  P.W = cfg->window;
-  P.M = cfg->mbox_cap;
-  P.D = cfg->max_delay + 2u;
-  P.NS = N + 1u;
-  P.WK = wl->outstanding;
-  P.wk_magic = 0xFFFFFFFFu / P.WK;
-  P.max_requests = wl->max_requests;
-  P.clusters = cfg->clusters;
-  P.cluster_base = cfg->cluster_base;
-  P.seed = cfg->seed;
-  P.q1 = cfg->q1;
-  P.q2 = cfg->q2;
-  P.fz = cfg->fz;
-  P.thrifty = cfg->thrifty;
-  P.ephemeral = cfg->ephemeral_leader;
-  P.rwc = cfg->reply_when_commit;
-  if (cfg->protocol == PAXISIM_WPAXOS) {
-    // kpaxos: Q1/Q2 from fz (wpaxos/kpaxos.go:15-27); no ReplyWhenCommit option
-    // (kpaxos.go:35-39); the Paxos replica's -ephemeral_leader is not consulted
-    P.q1 = cfg->fz ? PAXISIM_Q_FGRID_Q1 : PAXISIM_Q_GRID_ROW;
-    P.q2 = cfg->fz ? PAXISIM_Q_FGRID_Q2 : PAXISIM_Q_GRID_COLUMN;
-    P.rwc = 0;
-    P.ephemeral = 0;
-  }
-  P.variant = cfg->protocol == PAXISIM_WPAXOS ? variant : cfg->protocol;
-  if (P.variant == PAXISIM_M2PAXOS || P.variant == PAXISIM_KPAXOS) {   // m2paxos/kpaxos.go:15-21; paxos.NewPaxos default
-    P.q1 = PAXISIM_Q_MAJORITY;
-    P.q2 = PAXISIM_Q_MAJORITY;
-  }
-  if (P.variant == PAXISIM_M2PAXOS) P.adaptive = 1;
-  P.key_min = wl->key_min;
-  P.kspace = key_space_of(cfg, wl);
-  P.kspace_magic = 0xFFFFFFFFu / P.kspace;
-  P.conflict_key = wl->key_min ? P.kspace : 0u;
-  P.key_tail = wl->distribution == PAXISIM_DIST_TABLE ? wl->key_tail : 0u;
-  P.move_every = wl->move_every;
-  P.move_tables = wl->move_every ? wl->move_tables : 0u;
-  P.move_loop = wl->move_every ? wl->move_loop : 0u;
-  P.kv = cfg->protocol != PAXISIM_ABD && cfg->kv ? 1u : 0u;   // m2paxos/replica.go:34-52 has no -adaptive switch
-  P.max_delay = cfg->max_delay;
-  P.drop_ppm = fp->drop_ppm;
-  P.drop_len = fp->drop_len;
-  P.slow_ppm = fp->slow_ppm;
-  P.slow_len = fp->slow_len;
-  P.slow_min = fp->slow_min;
-  P.slow_max = fp->slow_max;
-  uint32_t r = 0;
-  for (uint32_t z = 0; z < P.Z; z++) {
-    P.npz[z] = cfg->npz[z];
-    P.zmask[z] = ((1u << cfg->npz[z]) - 1u) << r;
-    for (uint32_t k = 0; k < cfg->npz[z]; k++, r++) {
-      P.zone_of[r] = z;
-      h->zone_of[r] = z + 1;
-      h->node_of[r] = k + 1;
-    }
-    P.zfirst[z] = r - cfg->npz[z];
-  }
-  for (uint32_t w = 0; w < PAXISIM_MAX_WORKERS; w++) {
-    P.target[w] = wl->target[w];
-    P.start_step[w] = w < wl->outstanding ? wl->start_step[w] : 0u;
-    if (P.start_step[w]) P.late_workers |= 1u << w;
-  }
-
-  P.keys_magic = 0xFFFFFFFFu / P.keys;
-  for (uint32_t w = 0; w < PAXISIM_MAX_WORKERS; w++) {
-    const uint32_t z = w < P.WK ? P.zone_of[P.target[w] < N ? P.target[w] : 0u] : 0u;
-    P.wzone[w] = z;
-    P.wnk[w] = z < P.keys ? (P.keys - z + P.Z - 1u) / P.Z : 0u;
-    P.wnk_magic[w] = P.wnk[w] ? 0xFFFFFFFFu / P.wnk[w] : 0u;
-  }
-  // WPaxos: the instance scalars move into the tile image when one tile's
-  // image (and the agreement counts) fits the LDS; PAXISIM_WLDS=0 keeps them in HBM (A/B)
-  if (P.protocol == PAXISIM_WPAXOS) {
-    // The serial kernel keeps the image in HBM, where the packed 32-B table
-    // (wst, one line per bind) moves 0.67x the bytes of the image's word
-    // planes at the same speed (A/B r4, config 5: 267 vs 400 GB per launch,
-    // profiles/r4/config5_layout.json); PAXISIM_WLDS=0/1 overrides (A/B).
-    const char* ev = getenv("PAXISIM_WLDS");
-    const uint32_t agn = P.AR ? (2u * N * LANES + 15u) & ~15u : 0u;
-    const bool ser = serial_for(P.protocol);
-    P.wlds = (ev ? atoi(ev) != 0 : !ser) &&
-             (ser || proto_image(P.protocol, N, P.W, P.keys, P.WK, P.D, 1, false).bytes + agn <= LDS_MAX);
-    // Each instance's 32-B scalars and its window in one block of whole lines: a
-    // layout only, the kernels address both through wst_str / wlog_str.  On by default at W = 8, where
-    // six of the eight entries share the line the bind loads (mirrored A/B r6g2, config 5: +4.2% over
-    // the packed table at W = 8); at W = 16 it is 6% slower (r6g1).  PAXISIM_WCOLOC=0/1 overrides.
-    const char* cv = getenv("PAXISIM_WCOLOC");
-    P.wcoloc = !P.wlds && (cv ? atoi(cv) != 0 : P.W == 8u);
-  }
-  // Multi-Paxos: the window layout goes with the kernel - 16-B entries in plog for the serial units
-  // that take them (paxos_packed), else the image's planes (paxos_kernel.h)
-  P.packed = P.protocol == PAXISIM_PAXOS && serial_for(P.protocol) && paxos_packed(N);
-  P.img = proto_image(P.protocol, N, P.W, P.keys, P.WK, P.D, P.wlds, P.packed != 0);
-  {
-    // Cluster groups per workgroup (sim_core.h): as many 64-cluster tiles as
-    // the step kernel's registers leave wave slots for on every SIMD
-    // (ceil(G*N/4) <= waves per SIMD) and the LDS holds, at most 4.
-    int vgprs = 0, maxthr = 0;
-    const bool serial = serial_for(P.protocol);
-    h->ops = step_ops_for(P.protocol, N, P.wlds != 0, serial);
-    if (h->ops.attrs(&vgprs, &maxthr) != hipSuccess || vgprs <= 0) vgprs = 512;
-    if (maxthr <= 0) maxthr = (int)(N * LANES);
-    const uint32_t alloc = ((uint32_t)vgprs + 7u) / 8u * 8u;
-    const uint32_t wps = alloc >= 512u ? 1u : (512u / alloc < 8u ? 512u / alloc : 8u);
-    // per tile: the image, the agreement-ring arrival counts (not persisted:
-    // drained every step), then the stage
-    const uint32_t agn = P.AR ? (2u * N * LANES + 15u) & ~15u : 0u;
-    const uint32_t base = P.img.bytes + agn;
-    uint32_t G = 1, gmax = 4;
-    if (const char* e = getenv("PAXISIM_GROUPS")) gmax = (uint32_t)atoi(e) ? (uint32_t)atoi(e) : 1u;   // tuning
-    for (uint32_t g = 2; g <= gmax; g++)
-      if ((g * N + 3u) / 4u <= wps && g * N * LANES <= (uint32_t)maxthr && g * base <= LDS_MAX) G = g;
-    P.G = G;
-    // LDS stage for the first J picks of every replica's step, from what the groups leave
-    uint32_t jmax = 16;
-    if (const char* e = getenv("PAXISIM_STAGE")) jmax = (uint32_t)atoi(e);   // tuning override
-    const uint32_t room = LDS_MAX / G > base ? (LDS_MAX / G - base) / (N * LANES * 16u) : 0u;
-    P.J = room < jmax ? room : jmax;
-    if (!h->ops.staged) P.J = 0;   // that instance has no staged loop
-    P.off_agn = P.img.bytes;
-    P.off_stage = base;
-    P.lds_bytes = base + P.J * N * LANES * 16u;
-    if (serial) {   // one tile per workgroup; LDS: the image tail and the arrival counts
-      P.G = 1;
-      P.J = 0;
-      P.lds_tail = PXS_CLIENT_LDS ? P.img.off_wcur : P.img.off_poison;
-      P.lds_bytes = base - P.lds_tail;
-      if (PXS_WP_SCRATCH && P.protocol == PAXISIM_WPAXOS && P.wlds) {   // the replica-step instance scratch (wpaxos_kernel.h)
-        P.off_wscr = base;
-        P.lds_bytes += P.keys * WP_WORDS * LANES * 4u;
-      }
-      // phase binning (Paxos, with compaction): per-residue record counts after the rest
-      const char* pe = getenv("PAXISIM_PHASE_SORT");
-      const char* pp = getenv("PAXISIM_PHASE_PERIOD");
-      const char* ce = getenv("PAXISIM_COMPACT");
-      if (P.protocol == PAXISIM_PAXOS && !(ce && atoi(ce) == 0) && (pe ? atoi(pe) != 0 : PXS_PHASE_SORT)) {
-        P.phase_period = pp ? (uint32_t)atoi(pp) : 3u;
-        if (P.phase_period < 2u || P.phase_period > 7u) { delete h; return fail(PAXISIM_EINVAL, "PAXISIM_PHASE_PERIOD in [2,7]"); }
-        P.ph_rel = P.lds_tail + P.lds_bytes - P.img.off_cnt;
-        P.lds_bytes += P.phase_period * LANES * 4u;
-        P.phase_sort = 1;
-      }
-      // check_config bounds the image tail and the arrival counts; the phase
-      // counts come on top of them: refuse here, not at the first launch
-      if (P.lds_bytes > LDS_MAX) {
-        const uint32_t b = P.lds_bytes;
-        delete h;
-        return fail(PAXISIM_EUNSUPP, "serial LDS %u B (image tail, arrival and phase counts) exceeds LDS (%u B): "
-                    "reduce window/max_delay/replicas or set PAXISIM_PHASE_SORT=0", b, LDS_MAX);
-      }
-    }
-  }
-  P.C = (cfg->clusters + LANES * P.G - 1) / (LANES * P.G) * (LANES * P.G);
-  const size_t C = P.C, NC = (size_t)N * C, NIC = (size_t)P.NI * C, blocks = C / LANES;
-  const bool wp = P.protocol == PAXISIM_WPAXOS;
-  P.rec_per_block = P.D * N * P.NS * P.M * LANES;
-  // size the arena (rec last: it is the only region not zeroed)
-  size_t zero_bytes = 0, total = 0;
-  auto layout = [&](char* p, bool assign) {
-    uint32_t* s7 = carve<uint32_t>(p, NC * 7);
-    uint64_t* dg = carve<uint64_t>(p, NC);
-    uint32_t* kc = carve<uint32_t>(p, C);
-    uint32_t* pend = carve<uint32_t>(p, wp ? 0 : NC * PMAX);
-    uint32_t* fwd = carve<uint32_t>(p, NC * FMAX);
-    uint32_t* links = carve<uint32_t>(p, NC * N * 2);
-    uint32_t* cke = carve<uint32_t>(p, NIC * CKR);
-    uint64_t* ckd = carve<uint64_t>(p, NIC * CKR);
-    uint4* gst = carve<uint4>(p, NIC * GMAX);
-    uint32_t* st = carve<uint32_t>(p, NC * NSTAT);
-    uint32_t* reqx = carve<uint32_t>(p, wp || P.packed ? 0 : NC * P.W);
-    uint4* plog = carve<uint4>(p, P.packed ? NC * P.W : 0);
-    // WPaxos instances: the scalars table and the windows apart, or (wcoloc) one block per instance
-    // holding both - 32 B of scalars, then the window - padded to whole 128-B lines, so the entries
-    // at the window's head share the line the bind loads
-    const bool coloc = wp && !P.wlds && P.wcoloc;
-    const size_t wblk_b = ((32u + 16u * P.W) + 127u) & ~size_t(127);
-    uint4* wblk = carve<uint4>(p, coloc ? NIC * (wblk_b / 16u) : 0);
-    uint4* wst = carve<uint4>(p, wp && !P.wlds && !coloc ? NIC * 2 : 0);
-    uint64_t* wdig = carve<uint64_t>(p, wp && P.wlds ? NIC : 0);
-    uint32_t* wlog = carve<uint32_t>(p, wp && !coloc ? NIC * P.W * 4 : 0);
-    if (coloc) {
-      wst = wblk;
-      wlog = reinterpret_cast<uint32_t*>(wblk) + 8;
-    }
-    uint32_t* wpend = carve<uint32_t>(p, wp ? NIC * PMAX : 0);
-    uint4* wpx = carve<uint4>(p, wp && cfg->policy != PAXISIM_POLICY_CONSECUTIVE ? NIC * 3 : 0);
-    uint4* hist = carve<uint4>(p, NC * P.H);
-    uint32_t* maps = carve<uint32_t>(p, C * 4);
-    uint32_t* phs = carve<uint32_t>(p, C);
-    unsigned long long* agr = carve<unsigned long long>(p, (size_t)P.AR * P.NK * C);
-    uint4* agq = carve<uint4>(p, P.AR ? (size_t)2 * AGMAX * N * C : 0);
-    const bool ep = P.protocol == PAXISIM_EPAXOS;
-    uint4* ep_inst = carve<uint4>(p, ep ? (size_t)N * N * P.W * C * 4 : 0);
-    uint32_t* ep_sce = carve<uint32_t>(p, ep ? (size_t)3 * N * N * C : 0);
-    uint32_t* ep_cf = carve<uint32_t>(p, ep ? (size_t)2 * N * P.keys * N * C : 0);
-    uint32_t* ep_max = carve<uint32_t>(p, ep ? (size_t)P.keys * N * C : 0);
-    uint32_t* kv_val = carve<uint32_t>(p, P.kv ? (size_t)P.keys * N * C : 0);
-    uint32_t* kv_ver = carve<uint32_t>(p, P.kv ? (size_t)N * C : 0);
-    uint32_t* wrep = carve<uint32_t>(p, (size_t)P.WK * C);
-    uint8_t* image = carve<uint8_t>(p, blocks * P.img.bytes);
-    char* zend = p;
-    uint4* rec = carve<uint4>(p, blocks * P.rec_per_block);
-    if (assign) {
-      P.ballot = s7; P.slot = s7 + NC; P.execute = s7 + 2 * NC; P.meta = s7 + 3 * NC;
-      P.flags = s7 + 4 * NC; P.npend = s7 + 5 * NC; P.nfwd = s7 + 6 * NC;
-      P.digest = dg; P.kc = kc; P.pend = pend; P.fwd = fwd;
-      P.link_drop = links; P.link_slow = links + NC * N;
-      P.ck_e = cke; P.ck_d = ckd; P.stats = st; P.reqx = reqx; P.plog = plog; P.hist = hist; P.image = image; P.rec = rec;
-      P.wst = wst; P.wdig = wdig; P.wlog = wlog; P.wpend = wpend; P.gst = gst; P.wpx = wpx;
-      P.wst_str = coloc ? (uint32_t)(wblk_b / 16u) : 2u;
-      P.wlog_str = coloc ? (uint32_t)(wblk_b / 4u) : P.W * 4u;
-      P.slot_of = maps; P.cl_of = maps + C; P.frz = maps + 2 * C; P.qf = maps + 3 * C;
-      P.phase = phs;
-      P.agr = agr;
-      P.agq = agq;
-      P.ep_inst = ep_inst; P.ep_sce = ep_sce; P.ep_cf = ep_cf; P.ep_max = ep_max;
-      P.kv_val = kv_val; P.kv_ver = kv_ver; P.wrep = wrep;
-    }
-    return std::make_pair((size_t)zend, (size_t)p);
-  };
-  {
-    auto sz = layout(nullptr, false);
-    zero_bytes = sz.first;
-    total = sz.second;
-  }
-  // Arena placement experiments (the two run modes): PAXISIM_ARENA_PAD_MB
-  // reserves that much device memory first and frees it once the arena is placed;
-  // PAXISIM_ARENA_CONTIG=1 asks for physically contiguous memory.  Placement only.
-  void* pad = nullptr;
-  if (const char* ev = getenv("PAXISIM_ARENA_PAD_MB"))
-    if (atoll(ev) > 0) (void)hipMalloc(&pad, (size_t)atoll(ev) << 20);
-  const char* cev = getenv("PAXISIM_ARENA_CONTIG");
-  hipError_t e = cev && atoi(cev) ? hipExtMallocWithFlags(&h->arena, total, hipDeviceMallocContiguous)
-                                  : hipMalloc(&h->arena, total);
-  if (pad) (void)hipFree(pad);
-  if (e != hipSuccess) {
-    delete h;
-    return fail(PAXISIM_ENOMEM, "hipMalloc(%zu bytes) failed: %s", total, hipGetErrorString(e));
-  }
-  h->arena_bytes = total;
-  layout((char*)h->arena, true);
-  int rc1 = 0;
-  const size_t ncmp = CM_SUMS + (cfg->clusters + CB - 1) / CB;
-  if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipMalloc(&h->d_scratch, sizeof(uint64_t) * 64)) != hipSuccess ||
-      (e = hipMalloc(&h->pool[0].d_cmp, sizeof(uint32_t) * ncmp)) != hipSuccess ||
-      (e = hipMalloc(&h->pool[0].d_pairs, sizeof(uint32_t) * 2 * (C / 2 + LANES))) != hipSuccess ||
-      (e = hipMalloc(&h->pool[0].d_ph, sizeof(uint32_t) * (PH_SUMS + 2 * ((cfg->clusters + CB - 1) / CB)))) != hipSuccess ||
-      (e = hipMalloc(&h->d_faults, sizeof(DevFault) * PAXISIM_MAX_FAULTS)) != hipSuccess ||
-      (e = hipMemsetAsync(h->arena, 0, zero_bytes, h->stream)) != hipSuccess)
-    rc1 = fail(PAXISIM_EDEVICE, "device setup failed: %s", hipGetErrorString(e));
-  if (!rc1 && P.move_every) {   // the moving-Mu tables (the caller's buffer is not kept)
-    const size_t mb = (size_t)P.move_tables * PAXISIM_MAX_KEYS * sizeof(uint32_t);
-    if ((e = hipMalloc(&h->d_move, mb)) != hipSuccess ||
-        (e = hipMemcpy(h->d_move, wl->move_cdf, mb, hipMemcpyHostToDevice)) != hipSuccess)
-      rc1 = fail(PAXISIM_EDEVICE, "move_cdf upload failed: %s", hipGetErrorString(e));
-    P.move_cdf = h->d_move;
-  }
-  h->wl.move_cdf = nullptr;
-  if (!rc1) {
-    P.faults = h->d_faults;
-    P.bound = h->pool[0].d_cmp;
-    h->pool[0].stream = h->stream;
-    h->pool[0].end = (uint32_t)C;
-    // compaction: Paxos (the swap covers its arrays); PAXISIM_COMPACT=0 turns it off (A/B)
-    const char* ce = getenv("PAXISIM_COMPACT");
-    P.compact = cfg->protocol == PAXISIM_PAXOS && !(ce && atoi(ce) == 0);
-    for (uint32_t w = 0; w < wl->outstanding; w++)
-      if (P.start_step[w] + 1u > h->late_until) h->late_until = P.start_step[w] + 1u;
-    // pipelined launches (serial kernels): PAXISIM_PIPE = chunks per launch at most (1: off; default 4)
-    if (const char* pe = getenv("PAXISIM_PIPE")) h->pipe_max = (uint32_t)atoi(pe) ? (uint32_t)atoi(pe) : 1u;
-    if (h->pipe_max > 1 && h->ops.serial && h->ops.launch_pipe) {
-      uint32_t xcc[64] = {0};
-      const size_t nq = 16 + (C / LANES > 64 ? C / LANES : 64);   // the probe writes 64 words after the header
-      if ((e = hipMalloc(&h->pool[0].d_pipe, sizeof(uint32_t) * nq)) != hipSuccess ||
-          (e = hipMemsetAsync(h->pool[0].d_pipe, 0, sizeof(uint32_t) * 16, h->stream)) != hipSuccess)
-        rc1 = fail(PAXISIM_EDEVICE, "pipelined launch setup failed: %s", hipGetErrorString(e));
-      if (!rc1) {
-        // the poll limit of a chunk wait (sim_core.h pipe_item); PAXISIM_PIPE_SPIN sets it for tests
-        uint32_t spin = PXS_PIPE_SPIN_DEFAULT;
-        if (const char* se = getenv("PAXISIM_PIPE_SPIN")) spin = (uint32_t)strtoul(se, nullptr, 0);
-        if ((e = hipMemcpyAsync(h->pool[0].d_pipe + 9, &spin, sizeof spin, hipMemcpyHostToDevice, h->stream)) != hipSuccess)
-          rc1 = fail(PAXISIM_EDEVICE, "pipelined launch setup failed: %s", hipGetErrorString(e));
-      }
-      if (!rc1) {
-        xcc_probe<<<64, 64, 0, h->stream>>>(h->pool[0].d_pipe + 16);
-        if ((e = hipGetLastError()) != hipSuccess ||
-            (e = hipMemcpyAsync(xcc, h->pool[0].d_pipe + 16, sizeof xcc, hipMemcpyDeviceToHost, h->stream)) != hipSuccess ||
-            (e = hipStreamSynchronize(h->stream)) != hipSuccess)
-          rc1 = fail(PAXISIM_EDEVICE, "XCD probe failed: %s", hipGetErrorString(e));
-        for (uint32_t b = 0; b < 64 && !rc1; b++)     // round robin over 8 XCDs, any rotation
-          if ((xcc[b] & 7u) != ((xcc[0] + b) & 7u) || xcc[b] > 7u) h->pipe_max = 1;
-      }
-    } else {
-      h->pipe_max = 1;
-    }
-    // pipelined (PAXISIM_PIPE > 1, the default): compaction every three chunks (at most pipe_max), so
-    // they fuse (A/B r5v / r5x, config 2: 50-step chunks with compaction every 100 +2.0% against every
-    // 50 unpipelined, every 200 with four chunks +0.0%; 25-step chunks every 75 another +0.9 / +2.2%
-    // in the two run modes, every 50 +0.5 / +1.1%)
-    if (h->pipe_max > 1 && h->ops.serial && h->ops.launch_pipe) h->cmp_every = (h->pipe_max < 3u ? h->pipe_max : 3u) * h->S;
-    if (const char* ev = getenv("PAXISIM_COMPACT_EVERY")) h->cmp_every = (uint32_t)atoi(ev) ? (uint32_t)atoi(ev) : 1u;
-    if (const char* se = getenv("PAXISIM_PIPE_SLOTS")) h->pipe_slots = (uint32_t)strtoul(se, nullptr, 0);
-    if (!rc1) rc1 = pools_setup(h);
-    // every pool's bound: the clusters of its region
-    uint32_t b0 = (uint32_t)cfg->clusters;
-    h->bound_host = b0;
-    for (uint32_t p = h->npools; p-- > 1 && e == hipSuccess;)
-      e = hipMemcpyAsync(h->pool[p].d_cmp, &b0, sizeof b0, hipMemcpyHostToDevice, h->stream);
-    if (h->npools > 1) b0 = h->pool[0].end;
-    if (e == hipSuccess) e = hipMemcpyAsync(h->pool[0].d_cmp, &b0, sizeof b0, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) init_kernel<<<(unsigned)((C + 255) / 256), 256, 0, h->stream>>>(P);
-    if (e != hipSuccess || (e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(h->stream)) != hipSuccess)
-      rc1 = fail(PAXISIM_EDEVICE, "init kernel failed: %s", hipGetErrorString(e));
-  }
-  if (rc1) {
+  if (const int rc = create_on_device(h, kn, variant, N)) {
     paxisim_destroy(h);
-    return rc1;
+    return rc;
   }
   *out = h;
   return 0;

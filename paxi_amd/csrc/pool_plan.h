@@ -84,6 +84,17 @@ inline uint32_t pool_split_tile(uint32_t tiles, uint64_t clusters) {
   return s == 0 || (uint64_t)s * 64u >= clusters ? 0u : s;
 }
 
+// How many pools a handle asks for.  can: it compacts and runs pipelined serial launches - every
+// other handle runs one.  knob: PAXISIM_POOLS (1 or 2; 0 unset).  Without it a 5-replica handle takes
+// two when its tiles are at least four times the resident wave slots (0: not known).
+// pool_want_asks_slots: whether the answer depends on resident_slots (else the caller skips its
+// device queries).
+inline bool pool_want_asks_slots(int knob, bool can, uint32_t N) { return can && !knob && N == 5; }
+inline uint32_t pool_want(int knob, bool can, uint32_t N, uint32_t tiles, uint32_t resident_slots) {
+  if (pool_want_asks_slots(knob, can, N)) return resident_slots > 0 && tiles >= 4u * resident_slots ? 2u : 1u;
+  return can && knob ? (uint32_t)knob : 1u;
+}
+
 // Length of the union of [start, end] intervals (any order): the time at least one launch ran.
 inline double interval_union(std::vector<std::pair<double, double>> iv) {
   for (size_t a = 1; a < iv.size(); a++)   // insertion sort by start: a call has few launches
