@@ -257,6 +257,29 @@ TRACE_PROTOTYPES = {
     "paxisim_trace_totals": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
 }
 
+# Snapshot, restore and fork (include/paxisim_snapshot.h), likewise
+SNAPSHOT_SECTIONS = ("plan", "faults", "pools", "arena", "mailbox", "lat", "chist", "mv", "trace")
+SNAPSHOT_HEADER = 256
+SNAP_HAS_LAT, SNAP_HAS_CHIST, SNAP_HAS_MV, SNAP_HAS_TRACE = 1, 2, 4, 8
+
+
+class SnapshotInfo(C.Structure):
+    """struct paxisim_snapshot_info: what a snapshot's header says (paxisim_snapshot_info)."""
+    _fields_ = [("version", C.c_uint32), ("protocol", C.c_uint32), ("n_replicas", C.c_uint32), ("step", C.c_uint32),
+                ("clusters", C.c_uint64), ("cluster_base", C.c_uint64), ("mailbox_records", C.c_uint64),
+                ("total_bytes", C.c_uint64), ("plan_hash", C.c_uint64), ("recorders", C.c_uint32),
+                ("n_faults", C.c_uint32), ("section_bytes", C.c_uint64 * len(SNAPSHOT_SECTIONS)),
+                ("build_id", C.c_char * 32)]
+
+
+SNAPSHOT_PROTOTYPES = {
+    "paxisim_snapshot_size": [C.c_void_p, C.POINTER(C.c_uint64)],
+    "paxisim_snapshot": [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)],
+    "paxisim_restore": [C.c_void_p, C.c_void_p, C.c_uint64],
+    "paxisim_fork": [C.c_void_p, C.POINTER(C.c_void_p)],
+    "paxisim_snapshot_info": [C.c_void_p, C.c_uint64, C.POINTER(SnapshotInfo)],
+}
+
 
 # C prototypes shared by the product library (prefix "paxisim") and the oracle ("oracle").
 def declare(lib, prefix):

@@ -116,6 +116,12 @@ def load_library():
             fn = getattr(L, name)
             fn.restype = C.c_int
             fn.argtypes = args
+    # snapshot, restore and fork: likewise
+    if hasattr(L, "paxisim_snapshot"):
+        for name, args in abi.SNAPSHOT_PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.restype = C.c_int
+            fn.argtypes = args
     if L.paxisim_abi_version() != abi.ABI_VERSION:
         raise PaxisimError("ABI version mismatch between paxi_amd/abi.py and libpaxisim.so")
     _lib = L
@@ -138,7 +144,8 @@ EXPORTED = ["paxisim_abi_version", "paxisim_build_id", "paxisim_last_error", "pa
             "paxisim_client_history_enable", "paxisim_client_history", "paxisim_client_history_load",
             "paxisim_client_linearizable",
             "paxisim_multiversion_enable", "paxisim_kv_history", "paxisim_consensus", "paxisim_consensus_failed",
-            "paxisim_trace_enable", "paxisim_trace_read", "paxisim_trace_totals"]
+            "paxisim_trace_enable", "paxisim_trace_read", "paxisim_trace_totals",
+            "paxisim_snapshot_size", "paxisim_snapshot", "paxisim_restore", "paxisim_fork", "paxisim_snapshot_info"]
 
 
 def consensus_of_histories(histories):
@@ -448,6 +455,47 @@ class Simulation:
         k, d = C.c_uint64(), C.c_uint64()
         _check(self._trace("paxisim_trace_totals")(self.h, C.byref(k), C.byref(d)))
         return k.value, d.value
+
+    # snapshot, restore and fork
+    @staticmethod
+    def _snap(name):
+        fn = getattr(load_library(), name, None)
+        if fn is None:
+            raise PaxisimError(f"{LIB_PATH} was built without {name} (snapshot, restore and fork)")
+        return fn
+
+    def snapshot_size(self):
+        """The exact size in bytes of a snapshot taken now."""
+        n = C.c_uint64()
+        _check(self._snap("paxisim_snapshot_size")(self.h, C.byref(n)))
+        return n.value
+
+    def snapshot(self):
+        """The handle's whole simulation state at this step, as a numpy uint8 array (the blob of
+        include/paxisim_snapshot.h; of the mailboxes only the live records)."""
+        import numpy as np
+        blob = np.empty(self.snapshot_size(), dtype=np.uint8)
+        n = C.c_uint64()
+        _check(self._snap("paxisim_snapshot")(self.h, blob.ctypes.data_as(C.c_void_p), blob.nbytes, C.byref(n)))
+        assert n.value == blob.nbytes
+        return blob
+
+    def restore(self, blob):
+        """Overwrite the handle's state with a snapshot's: of the same build, plan and recorders
+        (else PaxisimError, and the handle is unchanged).  Restoring a handle's own snapshot rewinds it."""
+        import numpy as np
+        blob = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob)
+        _check(self._snap("paxisim_restore")(self.h, blob.ctypes.data_as(C.c_void_p), blob.nbytes))
+
+    def fork(self):
+        """A second, independent Simulation on the same device at the same state (device to device)."""
+        h = C.c_void_p()
+        _check(self._snap("paxisim_fork")(self.h, C.byref(h)))
+        f = object.__new__(Simulation)
+        f.cfg, f.wl, f.fp, f.N, f.h = self.cfg, self.wl, self.fp, self.N, h
+        if hasattr(self, "_mv_cap"):
+            f._mv_cap = self._mv_cap
+        return f
 
     def close(self):
         if self.h:
