@@ -280,6 +280,27 @@ SNAPSHOT_PROTOTYPES = {
     "paxisim_snapshot_info": [C.c_void_p, C.c_uint64, C.POINTER(SnapshotInfo)],
 }
 
+# Per-cluster verdict words and the search over them (include/paxisim_verdict.h),
+# likewise.  Bits 0..7 of a word are the F_* flags above.
+V_FLAGS = 0xFF
+V_AGREE, V_CONSENSUS, V_LIN, V_CLIENT_LIN, V_LIN_SKIPPED, V_TRUNCATED = (1 << b for b in range(8, 14))
+V_QUIET, V_WAITING, V_STALLED = (1 << b for b in range(16, 19))
+V_SCANS = V_CONSENSUS | V_LIN | V_CLIENT_LIN
+V_ALL = 0x00073FFF
+# bit number -> name, for Simulation.verdict_counts
+V_NAMES = {0: "WOVF", 1: "GHOST", 2: "MBOX_OVF", 3: "PEND_OVF", 4: "UNFAITHFUL", 5: "POISON", 6: "BALLOT_OVF",
+           7: "HIST_OVF", 8: "AGREE", 9: "CONSENSUS", 10: "LIN", 11: "CLIENT_LIN", 12: "LIN_SKIPPED",
+           13: "TRUNCATED", 16: "QUIET", 17: "WAITING", 18: "STALLED"}
+
+VERDICT_PROTOTYPES = {
+    "paxisim_verdict_available": [C.c_void_p, C.POINTER(C.c_uint32)],
+    "paxisim_verdicts": [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p],
+    "paxisim_find": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)],
+    "paxisim_verdict_counts": [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)],
+    "paxisim_select_words": [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                             C.POINTER(C.c_uint64)],
+}
+
 
 # C prototypes shared by the product library (prefix "paxisim") and the oracle ("oracle").
 def declare(lib, prefix):

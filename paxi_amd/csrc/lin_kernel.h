@@ -757,6 +757,19 @@ struct LinAbd {
   __device__ static const uint4& op(const Params&, uint32_t, const uint4& o) { return o; }
 };
 
+// The local cluster id of the cluster a source walks at index c (the per-cluster marks of a scan are
+// indexed by id): LinAbd walks slots, every other source walks ids.
+template <class S>
+struct LinIdOf {
+  __device__ static uint64_t id(const Params&, uint64_t c) { return c; }
+};
+template <>
+struct LinIdOf<LinAbd> {
+  __device__ static uint64_t id(const Params& P, uint64_t c) { return P.cl_of[c]; }
+};
+// the marks' bit for "a partition of this cluster was skipped" (paxisim_verdict.h PAXISIM_V_LIN_SKIPPED)
+constexpr uint32_t LIN_MARK_SKIPPED = 0x1000u;
+
 // Canonical op index -> its history record (source-major; len[s] ops each).
 template <class S>
 __device__ __forceinline__ const uint4* hist_at(const Params& P, uint64_t c, const uint32_t* len, uint32_t idx) {
@@ -769,9 +782,12 @@ __device__ __forceinline__ const uint4* hist_at(const Params& P, uint64_t c, con
 // [grid][sources * per_source] ops, the cluster's history grouped by key (its own region of
 // the launch's workspace).  Dynamic LDS: LIN_LW sort buffers (LIN_SORT_BYTES);
 // partitions of at most LIN_SMAX ops are checked in registers (LinReg).
+// mark (may be null; then the scan is the totals-only one): [clusters] by cluster id, ORed with
+// mark_bit where the cluster adds to LIN_ANOM here and with LIN_MARK_SKIPPED where it adds to LIN_SKIP.
 template <class S>
 __global__ void __launch_bounds__(LIN_LW * 64, PXS_LIN_MINW) lin_cluster_kernel(Params P, uint64_t c0, uint4* stage_all,
-                                                                   unsigned long long* out, uint2* big) {
+                                                                   unsigned long long* out, uint2* big,
+                                                                   uint32_t* mark, uint32_t mark_bit) {
   extern __shared__ uint4 lds_lin[];
   __shared__ uint32_t len[S::MAX_SRC];
   __shared__ uint32_t cnt[LIN_LW][PAXISIM_MAX_KEYS];   // per wave slice, per key
@@ -844,7 +860,10 @@ __global__ void __launch_bounds__(LIN_LW * 64, PXS_LIN_MINW) lin_cluster_kernel(
     const uint32_t n = koff[k + 1] - koff[k];
     if (!n) continue;
     if (n > LIN_VMAX) {                                // beyond the bit sets: reported, not checked
-      if (lane_id() == 0) atomicAdd(&out[LIN_SKIP], 1ull);
+      if (lane_id() == 0) {
+        atomicAdd(&out[LIN_SKIP], 1ull);
+        if (mark) atomicOr(&mark[LinIdOf<S>::id(P, c)], LIN_MARK_SKIPPED);
+      }
       continue;
     }
     ops += n;
@@ -878,6 +897,7 @@ __global__ void __launch_bounds__(LIN_LW * 64, PXS_LIN_MINW) lin_cluster_kernel(
   }
   if (lane_id() == 0) {
     if (anomalies) atomicAdd(&out[LIN_ANOM], anomalies);
+    if (anomalies && mark) atomicOr(&mark[LinIdOf<S>::id(P, c)], mark_bit);
     if (ops) atomicAdd(&out[LIN_OPS], ops);
 #ifdef PXS_LIN_STAMPS
     for (int q = 0; q < 8; q++) atomicAdd(&out[LIN_NOUT + q], (unsigned long long)lst[q]);
@@ -887,10 +907,14 @@ __global__ void __launch_bounds__(LIN_LW * 64, PXS_LIN_MINW) lin_cluster_kernel(
 
 // grid-stride over the big partitions {stage offset, ops}: one wave each,
 // scratch in HBM (slot = blockIdx.x), capacity 64 * nw ops; WPL bit-set words
-// per lane (nw <= 64 * WPL).
+// per lane (nw <= 64 * WPL).  mark (may be null): the partition's cluster is the launch's first, c0, plus
+// its stage offset / cap (cap: a cluster's stage, in ops); idmap (null: the identity) takes that
+// index to the cluster id.
 template <int WPL>
 __global__ void __launch_bounds__(64) lin_big_kernel(const uint4* stage_all, const uint2* big, uint32_t nbig,
-                                                     uint8_t* ws, uint32_t nw, unsigned long long* out) {
+                                                     uint8_t* ws, uint32_t nw, unsigned long long* out,
+                                                     uint32_t* mark, uint32_t mark_bit, uint64_t c0, uint32_t cap,
+                                                     const uint32_t* idmap) {
   const LinScratch s = lin_scratch(ws + (size_t)blockIdx.x * lin_scratch_bytes(nw, false), nw, false);
   unsigned long long anomalies = 0;
   for (uint32_t b = blockIdx.x; b < nbig; b += gridDim.x) {
@@ -898,7 +922,12 @@ __global__ void __launch_bounds__(64) lin_big_kernel(const uint4* stage_all, con
     g.s = s;
     g.n = big[b].y;
     lin_sort<true>(stage_all + big[b].x, g.n, g.s);
-    anomalies += g.run();
+    const uint32_t a = g.run();
+    anomalies += a;
+    if (mark && a && lane_id() == 0) {
+      const uint64_t c = c0 + big[b].x / cap;
+      atomicOr(&mark[idmap ? (uint64_t)idmap[c] : c], mark_bit);
+    }
   }
   if (lane_id() == 0 && anomalies) atomicAdd(&out[LIN_ANOM], anomalies);
 }

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <utility>
 #include <algorithm>
 #include <vector>
@@ -28,6 +29,7 @@
 #include "snapshot_kernel.h"
 #include "snapshot_plan.h"
 #include "step_ops.h"
+#include "verdict_kernel.h"
 
 using namespace pxs;
 
@@ -327,41 +329,12 @@ __global__ void gather_inst_kernel(Params P, uint64_t lo, uint64_t n, paxisim_in
 
 // Agreement scan (client.go:279-320; tla/wpaxos.tla Safety): replicas that
 // executed the same number of slots must hold the same digest, and digest
-// checkpoints taken at the same executed count must agree.
+// checkpoints taken at the same executed count must agree.  The per-cluster body is verdict_kernel.h agree_bad, which the
+// verdict pass calls too, so the count and the PAXISIM_V_AGREE bit cannot drift apart.
 __global__ void check_kernel(Params P, uint64_t* out) {
   const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   uint64_t bad = 0;
-  if (c < P.clusters && P.protocol != PAXISIM_EPAXOS) {   // EPaxos: no single log (paxisim.h)
-    for (uint32_t r = 0; r < P.N; r++) bad |= P.stats[krc(P, ST_AGB, r, c)] != 0;   // running check (paxos_exec)
-    auto exec_digest = [&](uint32_t key, uint32_t r, uint32_t& e, uint64_t& d) {
-      if (P.protocol == PAXISIM_WPAXOS) {
-        uint4 a, b;
-        wp_read(P, c / LANES, key, r, (uint32_t)(c % LANES), a, b);
-        e = a.z;
-        d = (uint64_t)b.y | ((uint64_t)b.z << 32);
-      } else {
-        e = P.execute[rc(P, r, c)];
-        d = P.digest[rc(P, r, c)];
-      }
-    };
-    auto ck = [&](uint32_t k, uint32_t inst) { return ((size_t)k * P.NI + inst) * P.C + c; };
-    for (uint32_t key = 0; key < P.NK && !bad; key++)       // per Paxos instance (WPaxos: per key)
-      for (uint32_t a = 0; a < P.N && !bad; a++)
-        for (uint32_t b = a + 1; b < P.N && !bad; b++) {
-          uint32_t ea, eb;
-          uint64_t da, db;
-          exec_digest(key, a, ea, da);
-          exec_digest(key, b, eb, db);
-          if (ea == eb && da != db) bad = 1;
-          const uint32_t ia = key * P.N + a, ib = key * P.N + b;
-          for (uint32_t k = 0; k < CKR && !bad; k++) {
-            const uint32_t e = P.ck_e[ck(k, ia)];
-            if (!e) continue;
-            for (uint32_t j = 0; j < CKR && !bad; j++)
-              if (P.ck_e[ck(j, ib)] == e && P.ck_d[ck(k, ia)] != P.ck_d[ck(j, ib)]) bad = 1;
-          }
-        }
-  }
+  if (c < P.clusters && P.protocol != PAXISIM_EPAXOS) bad = agree_bad(P, c) ? 1u : 0u;   // EPaxos: no single log (paxisim.h)
   bad = wave_sum(bad);
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd((unsigned long long*)out, (unsigned long long)bad);
 }
@@ -1846,7 +1819,8 @@ extern "C" int paxisim_history_load(paxisim* h, uint64_t cluster, uint32_t repli
 // History.Linearizable over the history source S of every cluster (lin_kernel.h): LinAbd, the
 // replicas' completed ABD ops, or LinClient, the workers' ops of any protocol (chist_kernel.h).
 template <class S>
-static int lin_scan(paxisim* h, uint64_t* anomalies, uint64_t* ops, uint64_t* skipped) {
+static int lin_scan(paxisim* h, uint64_t* anomalies, uint64_t* ops, uint64_t* skipped, uint32_t* mark = nullptr,
+                    uint32_t mark_bit = 0) {
   if (const int jrc = enter(h)) return jrc;
   if (const int rc = pipe_check(h)) return rc;   // results only of launches that fully ran
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1881,7 +1855,7 @@ static int lin_scan(paxisim* h, uint64_t* anomalies, uint64_t* ops, uint64_t* sk
   for (uint64_t c0 = 0; e == hipSuccess && c0 < P.clusters; c0 += chunk) {
     const uint64_t nc = std::min<uint64_t>(chunk, P.clusters - c0);
     if ((e = hipMemsetAsync(out + LIN_BIG, 0, 2 * sizeof(unsigned long long), h->stream)) != hipSuccess) break;
-    lin_cluster_kernel<S><<<(unsigned)nc, LIN_LW * 64, lds, h->stream>>>(P, c0, stage, out, big);
+    lin_cluster_kernel<S><<<(unsigned)nc, LIN_LW * 64, lds, h->stream>>>(P, c0, stage, out, big, mark, mark_bit);
     unsigned long long bc[2] = {0, 0};
     if ((e = hipGetLastError()) != hipSuccess) break;
     if ((e = hipMemcpyAsync(bc, out + LIN_BIG, sizeof bc, hipMemcpyDeviceToHost, h->stream)) != hipSuccess) break;
@@ -1901,8 +1875,13 @@ static int lin_scan(paxisim* h, uint64_t* anomalies, uint64_t* ops, uint64_t* sk
         if ((e = hipMalloc(&bws, need)) != hipSuccess) break;
         bws_bytes = need;
       }
-      if (nw <= 64u) lin_big_kernel<1><<<waves, 64, 0, h->stream>>>(stage, big, (uint32_t)bc[0], bws, nw, out);
-      else lin_big_kernel<LIN_WPL_MAX><<<waves, 64, 0, h->stream>>>(stage, big, (uint32_t)bc[0], bws, nw, out);
+      const uint32_t* idmap = std::is_same<S, LinAbd>::value ? P.cl_of : nullptr;   // LinAbd walks slots
+      if (nw <= 64u)
+        lin_big_kernel<1><<<waves, 64, 0, h->stream>>>(stage, big, (uint32_t)bc[0], bws, nw, out, mark, mark_bit, c0,
+                                                       (uint32_t)cap, idmap);
+      else
+        lin_big_kernel<LIN_WPL_MAX><<<waves, 64, 0, h->stream>>>(stage, big, (uint32_t)bc[0], bws, nw, out, mark,
+                                                                 mark_bit, c0, (uint32_t)cap, idmap);
       if ((e = hipGetLastError()) != hipSuccess) break;
     }
   }
@@ -2631,6 +2610,184 @@ extern "C" int paxisim_fork(paxisim* h, paxisim** out) {
   if (f->npools > 1) f->main_ahead = true;   // the pools' streams wait for these copies
   *out = f;
   return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Per-cluster verdict words and the search over them (include/paxisim_verdict.h, DESIGN.md §3.17,
+// verdict_kernel.h)
+// ---------------------------------------------------------------------------
+static_assert(LIN_MARK_SKIPPED == PAXISIM_V_LIN_SKIPPED, "lin_kernel.h: the skipped mark is the verdict bit");
+static_assert(LIN_VMAX == 16384u, "include/paxisim_verdict.h: the partition size PAXISIM_V_LIN_SKIPPED speaks of");
+
+namespace {
+struct DevBuf {   // a device allocation freed at scope exit
+  void* p = nullptr;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  template <class T>
+  T* as() const { return static_cast<T*>(p); }
+  void* release() {
+    void* q = p;
+    p = nullptr;
+    return q;
+  }
+};
+}  // namespace
+
+static uint32_t verdict_bits(const paxisim* h) {
+  uint32_t b = PAXISIM_V_FLAGS | PAXISIM_V_QUIET | PAXISIM_V_WAITING | PAXISIM_V_STALLED;
+  if (h->P.protocol != PAXISIM_EPAXOS) b |= PAXISIM_V_AGREE;
+  if (h->P.mv_cap) b |= PAXISIM_V_CONSENSUS | PAXISIM_V_TRUNCATED;
+  if (h->P.protocol == PAXISIM_ABD && h->P.H) b |= PAXISIM_V_LIN | PAXISIM_V_LIN_SKIPPED;
+  if (h->P.ch_cap) b |= PAXISIM_V_CLIENT_LIN | PAXISIM_V_LIN_SKIPPED | PAXISIM_V_TRUNCATED;
+  return b;
+}
+
+// The scans a call asks for: refused before anything is launched.
+static int verdict_scans_ok(const paxisim* h, uint32_t scans) {
+  if (scans & ~PAXISIM_V_SCANS)
+    return fail(PAXISIM_EINVAL, "scans 0x%x: only CONSENSUS, LIN and CLIENT_LIN are scans", scans);
+  if ((scans & PAXISIM_V_LIN) && (h->P.protocol != PAXISIM_ABD || h->P.H == 0))
+    return fail(PAXISIM_EUNSUPP, "the LIN scan needs protocol ABD with history > 0");
+  if ((scans & PAXISIM_V_CLIENT_LIN) && !h->P.ch_cap)
+    return fail(PAXISIM_EUNSUPP, "the CLIENT_LIN scan needs paxisim_client_history_enable");
+  if ((scans & PAXISIM_V_CONSENSUS) && !h->P.mv_cap)
+    return fail(PAXISIM_EUNSUPP, "the CONSENSUS scan needs paxisim_multiversion_enable");
+  return 0;
+}
+
+// The verdict word of every cluster, evaluated now: *d_words is [clusters] on the device, complete
+// when this returns; the caller frees it.
+static int verdict_eval(paxisim* h, uint32_t scans, uint32_t** d_words) {
+  if (const int rc = quiesce(h)) return rc;
+  const Params& P = h->P;
+  const uint64_t n = P.clusters;
+  DevBuf words, marks, masks;
+  hipError_t e = hipMalloc(&words.p, n * sizeof(uint32_t));
+  if (e == hipSuccess && (scans & (PAXISIM_V_LIN | PAXISIM_V_CLIENT_LIN))) {
+    // (P.C entries: a slot-walking scan marks cl_of[slot], which is below C for every slot)
+    e = hipMalloc(&marks.p, P.C * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemsetAsync(marks.p, 0, P.C * sizeof(uint32_t), h->stream);
+  }
+  if (e == hipSuccess && (scans & PAXISIM_V_CONSENSUS)) {
+    e = hipMalloc(&masks.p, n * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemsetAsync(masks.p, 0, n * sizeof(unsigned long long), h->stream);
+  }
+  if (e != hipSuccess) return fail(PAXISIM_ENOMEM, "verdict buffers: %s", hipGetErrorString(e));
+  if (scans & PAXISIM_V_LIN)
+    if (const int rc = lin_scan<LinAbd>(h, nullptr, nullptr, nullptr, marks.as<uint32_t>(), PAXISIM_V_LIN)) return rc;
+  if (scans & PAXISIM_V_CLIENT_LIN)
+    if (const int rc = lin_scan<LinClient>(h, nullptr, nullptr, nullptr, marks.as<uint32_t>(), PAXISIM_V_CLIENT_LIN))
+      return rc;
+  if (scans & PAXISIM_V_CONSENSUS) {   // mv_scan's launch, its masks kept on the device
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(h->d_scratch);
+    const uint64_t pairs = n * P.keys;
+    const unsigned grid = (unsigned)std::min<uint64_t>((pairs + MV_WAVES - 1) / MV_WAVES, 8192);
+    HIPCHK(hipMemsetAsync(out, 0, MV_NOUT * sizeof(unsigned long long), h->stream));
+    mv_consensus_kernel<<<grid, MV_WAVES * 64, 0, h->stream>>>(P, 0, n, out, masks.as<unsigned long long>());
+    HIPCHK(hipGetLastError());
+  }
+  VerdictScans in;
+  in.mv_masks = masks.as<unsigned long long>();
+  in.marks = marks.as<uint32_t>();
+  in.scans = scans;
+  in.started = h->t >= h->late_until ? 1u : 0u;
+  verdict_kernel<<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(P, in, words.as<uint32_t>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(h->stream));   // the scans' buffers are freed on return
+  *d_words = static_cast<uint32_t*>(words.release());
+  return 0;
+}
+
+// The select over n device words on `stream` (verdict_kernel.h): the matching indices, ascending.
+static int select_run(hipStream_t stream, const uint32_t* d_words, uint64_t n, uint32_t any, uint32_t none,
+                      uint64_t* ids, uint64_t cap, uint64_t* total) {
+  *total = 0;
+  if (n == 0) return 0;
+  const uint64_t nwg = (n + SEL_WG - 1) / SEL_WG;
+  if (nwg > 0x7FFFFFFFull)
+    return fail(PAXISIM_ERANGE, "select: %llu words are more than one launch covers", (unsigned long long)n);
+  DevBuf offs, out;
+  hipError_t e = hipMalloc(&offs.p, (nwg + 1) * sizeof(unsigned long long));
+  if (e != hipSuccess) return fail(PAXISIM_ENOMEM, "select offsets: %s", hipGetErrorString(e));
+  unsigned long long* d_offs = offs.as<unsigned long long>();
+  unsigned long long tot = 0;
+  select_count<<<(unsigned)nwg, SEL_WG, 0, stream>>>(d_words, n, any, none, d_offs);
+  select_scan<<<1, SEL_SCAN, 0, stream>>>(d_offs, nwg, d_offs + nwg);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(&tot, d_offs + nwg, sizeof tot, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  *total = tot;
+  const uint64_t k = std::min<uint64_t>(tot, cap);
+  if (k == 0) return 0;
+  e = hipMalloc(&out.p, k * sizeof(unsigned long long));
+  if (e != hipSuccess) return fail(PAXISIM_ENOMEM, "select ids (%llu): %s", (unsigned long long)k, hipGetErrorString(e));
+  select_scatter<<<(unsigned)nwg, SEL_WG, 0, stream>>>(d_words, n, any, none, d_offs, out.as<unsigned long long>(), k);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(ids, out.p, k * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  return 0;
+}
+
+extern "C" int paxisim_verdict_available(paxisim* h, uint32_t* bits) {
+  if (!h || !bits) return fail(PAXISIM_EINVAL, "null argument");
+  if (const int rc = quiesce(h)) return rc;
+  *bits = verdict_bits(h);
+  return 0;
+}
+
+extern "C" int paxisim_verdicts(paxisim* h, uint32_t scans, uint64_t lo, uint64_t n, uint32_t* words) {
+  if (!h || (n && !words)) return fail(PAXISIM_EINVAL, "null argument");
+  if (const int rc = verdict_scans_ok(h, scans)) return rc;
+  if (lo > h->cfg.clusters || n > h->cfg.clusters - lo) return fail(PAXISIM_ERANGE, "cluster range");
+  if (n == 0) return 0;
+  DevBuf d;
+  if (const int rc = verdict_eval(h, scans, reinterpret_cast<uint32_t**>(&d.p))) return rc;
+  HIPCHK(hipMemcpyAsync(words, d.as<uint32_t>() + lo, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+extern "C" int paxisim_find(paxisim* h, uint32_t scans, uint32_t any, uint32_t none, uint64_t* ids, uint64_t cap,
+                            uint64_t* total) {
+  if (!h || !total || (cap && !ids)) return fail(PAXISIM_EINVAL, "null argument");
+  if ((any | none) & ~PAXISIM_V_ALL)
+    return fail(PAXISIM_EINVAL, "any 0x%x / none 0x%x: bits outside the defined ones", any, none);
+  if (const int rc = verdict_scans_ok(h, scans)) return rc;
+  DevBuf d;
+  if (const int rc = verdict_eval(h, scans, reinterpret_cast<uint32_t**>(&d.p))) return rc;
+  return select_run(h->stream, d.as<uint32_t>(), h->P.clusters, any, none, ids, cap, total);
+}
+
+extern "C" int paxisim_verdict_counts(paxisim* h, uint32_t scans, uint64_t counts[32]) {
+  if (!h || !counts) return fail(PAXISIM_EINVAL, "null argument");
+  if (const int rc = verdict_scans_ok(h, scans)) return rc;
+  DevBuf d, c;
+  if (const int rc = verdict_eval(h, scans, reinterpret_cast<uint32_t**>(&d.p))) return rc;
+  const uint64_t n = h->P.clusters;
+  hipError_t e = hipMalloc(&c.p, 32 * sizeof(unsigned long long));
+  if (e != hipSuccess) return fail(PAXISIM_ENOMEM, "verdict counts: %s", hipGetErrorString(e));
+  HIPCHK(hipMemsetAsync(c.p, 0, 32 * sizeof(unsigned long long), h->stream));
+  verdict_count_kernel<<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(d.as<uint32_t>(), n,
+                                                                         c.as<unsigned long long>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(counts, c.p, 32 * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+extern "C" int paxisim_select_words(int device, const uint32_t* words, uint64_t n, uint32_t any, uint32_t none,
+                                    uint64_t* ids, uint64_t cap, uint64_t* total) {
+  if (!total || (n && !words) || (cap && !ids)) return fail(PAXISIM_EINVAL, "null argument");
+  *total = 0;
+  if (n == 0) return 0;
+  HIPCHK(hipSetDevice(device));
+  DevBuf d;
+  hipError_t e = hipMalloc(&d.p, n * sizeof(uint32_t));
+  if (e != hipSuccess) return fail(PAXISIM_ENOMEM, "select words (%llu): %s", (unsigned long long)n, hipGetErrorString(e));
+  HIPCHK(hipMemcpy(d.p, words, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  return select_run(nullptr, d.as<uint32_t>(), n, any, none, ids, cap, total);
 }
 
 // ---------------------------------------------------------------------------

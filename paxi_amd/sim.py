@@ -122,6 +122,12 @@ def load_library():
             fn = getattr(L, name)
             fn.restype = C.c_int
             fn.argtypes = args
+    # per-cluster verdict words and the search over them: likewise
+    if hasattr(L, "paxisim_verdicts"):
+        for name, args in abi.VERDICT_PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.restype = C.c_int
+            fn.argtypes = args
     if L.paxisim_abi_version() != abi.ABI_VERSION:
         raise PaxisimError("ABI version mismatch between paxi_amd/abi.py and libpaxisim.so")
     _lib = L
@@ -145,7 +151,9 @@ EXPORTED = ["paxisim_abi_version", "paxisim_build_id", "paxisim_last_error", "pa
             "paxisim_client_linearizable",
             "paxisim_multiversion_enable", "paxisim_kv_history", "paxisim_consensus", "paxisim_consensus_failed",
             "paxisim_trace_enable", "paxisim_trace_read", "paxisim_trace_totals",
-            "paxisim_snapshot_size", "paxisim_snapshot", "paxisim_restore", "paxisim_fork", "paxisim_snapshot_info"]
+            "paxisim_snapshot_size", "paxisim_snapshot", "paxisim_restore", "paxisim_fork", "paxisim_snapshot_info",
+            "paxisim_verdict_available", "paxisim_verdicts", "paxisim_find", "paxisim_verdict_counts",
+            "paxisim_select_words"]
 
 
 def consensus_of_histories(histories):
@@ -160,6 +168,35 @@ def consensus_of_histories(histories):
         if len(present) > 1:
             return False, i
     return True, None
+
+
+def _select(fn, n, cap):
+    """Run a select call `fn(ids pointer or None, cap, total pointer)` so that it returns the first
+    `cap` matches, or every match when cap is None: (ids as a numpy uint64 array, total).  With cap
+    None the first call offers room for 65,536 ids, and only a larger total costs a second call."""
+    import numpy as np
+    tot = C.c_uint64()
+    room = min(n, 1 << 16) if cap is None else min(int(cap), n)
+    ids = np.empty(room, dtype=np.uint64)
+    fn(ids.ctypes.data_as(C.c_void_p) if room else None, room, C.byref(tot))
+    if cap is None and tot.value > room:
+        room = tot.value
+        ids = np.empty(room, dtype=np.uint64)
+        fn(ids.ctypes.data_as(C.c_void_p), room, C.byref(tot))
+    return ids[:min(room, tot.value)], tot.value
+
+
+def select_words(words, any, none=0, cap=None, device=0):
+    """paxisim_select_words: the indices i of `words` (uint32) with (any == 0 or words[i] & any) and
+    not words[i] & none, ascending, found on the device: (the first `cap` of them - all when cap is
+    None - as a numpy uint64 array, the exact number of matches)."""
+    import numpy as np
+    fn = getattr(load_library(), "paxisim_select_words", None)
+    if fn is None:
+        raise PaxisimError(f"{LIB_PATH} was built without paxisim_select_words (verdict words)")
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    ptr = w.ctypes.data_as(C.c_void_p) if w.size else None
+    return _select(lambda ids, k, tot: _check(fn(device, ptr, w.size, any, none, ids, k, tot)), w.size, cap)
 
 
 def _check(rc):
@@ -496,6 +533,47 @@ class Simulation:
         if hasattr(self, "_mv_cap"):
             f._mv_cap = self._mv_cap
         return f
+
+    # per-cluster verdict words and the search over them
+    @staticmethod
+    def _verdict(name):
+        fn = getattr(load_library(), name, None)
+        if fn is None:
+            raise PaxisimError(f"{LIB_PATH} was built without {name} (verdict words)")
+        return fn
+
+    def verdict_available(self):
+        """The abi.V_* / abi.F_* bits this handle can produce."""
+        b = C.c_uint32()
+        _check(self._verdict("paxisim_verdict_available")(self.h, C.byref(b)))
+        return b.value
+
+    def verdicts(self, scans=0, lo=0, n=None):
+        """The verdict words of local clusters [lo, lo + n) as a numpy uint32 array, evaluated now;
+        `scans`: which of abi.V_CONSENSUS | V_LIN | V_CLIENT_LIN to run (their bits are 0 otherwise)."""
+        import numpy as np
+        n = self.cfg.clusters - lo if n is None else n
+        w = np.empty(max(0, n), dtype=np.uint32)
+        _check(self._verdict("paxisim_verdicts")(self.h, scans, lo, n, w.ctypes.data_as(C.c_void_p) if w.size else None))
+        return w
+
+    def find(self, any, none=0, scans=None, cap=None, global_ids=False):
+        """The clusters whose verdict word has a bit of `any` (any == 0: every cluster) and none of
+        `none`, found on the device: (ids ascending as a numpy uint64 array - the first `cap`, all when
+        cap is None -, the exact number of matches).  `scans` defaults to the scan bits in any | none;
+        ids are local, or with global_ids have cfg.cluster_base added."""
+        scans = (any | none) & abi.V_SCANS if scans is None else scans
+        fn = self._verdict("paxisim_find")
+        ids, total = _select(lambda p, k, tot: _check(fn(self.h, scans, any, none, p, k, tot)), self.cfg.clusters, cap)
+        if global_ids:
+            ids = ids + ids.dtype.type(self.cfg.cluster_base)
+        return ids, total
+
+    def verdict_counts(self, scans=0):
+        """{bit name: clusters whose verdict word has the bit} (names: abi.V_NAMES)."""
+        c = (C.c_uint64 * 32)()
+        _check(self._verdict("paxisim_verdict_counts")(self.h, scans, c))
+        return {name: c[b] for b, name in abi.V_NAMES.items()}
 
     def close(self):
         if self.h:
