@@ -71,6 +71,6 @@ def test_unflagged_clusters_equal_a_wider_window(cfg_id, steps, fz, w):
             assert i16[c * N * I:(c + 1) * N * I] == i64[c * N * I:(c + 1) * N * I], f"cluster {c} instances"
     print(f"config {cfg_id} fz={fz}: {faithful}/{CLUSTERS} clusters unflagged at W={w}, "
           f"{touched} of them touched the window bound (WOVF/GHOST)")
-    assert faithful >= CLUSTERS // 2
+    assert faithful == CLUSTERS   # the oracle's count for every row: no cluster is UNFAITHFUL, as the bench lines report
     if cfg_id == 2:
         assert touched > 0        # the comparison covers clusters that hit the bound
