@@ -25,6 +25,11 @@ The claim: while neither UNFAITHFUL nor an overflow flag (MBOX_OVF, PEND_OVF, BA
 raised, the window, the ghost table and the forwards table equal the maps; WOVF and GHOST alone
 change nothing; POISON appears exactly where Go panics.
 
+`replay`, `words_of` and `check_end` also serve the per-key protocols (tests/wpaxos_model.py,
+DESIGN.md §3.5g): `replay` takes a replica factory, `words_of` accepts the key tag of P1a..P3 and
+LeaderChange there, and `check_end` then compares every (replica, key) instance of read_instances
+and its window, and read_state's aggregates over them.
+
 Simulator plumbing, not protocol, and shared with tests/epaxos_model.py: mix64 / fmix32 and the
 merge order of a step's inbox (`handled`).  Record encodings are those of DESIGN.md §3.1-3.2; the
 executed-history digest is the chain of include/paxisim.h ("hash chain of executed (slot,
@@ -38,7 +43,11 @@ from paxi_amd import abi, trace
 T_REQUEST, T_REPLY, T_P1A, T_P1B, T_P1B_ENTRY, T_P2A, T_P2B, T_P3 = (
     trace.T_REQUEST, trace.T_REPLY, trace.T_P1A, trace.T_P1B, trace.T_P1B_ENTRY, trace.T_P2A, trace.T_P2B,
     trace.T_P3)
+T_LEADERCHG = trace.T_LEADERCHG
 SOCKET_TYPES = (T_REQUEST, T_REPLY, T_P1A, T_P1B, T_P2A, T_P2B, T_P3)
+# the per-key protocols (tests/wpaxos_model.py): kpaxos.Broadcast / Send tag P1a..P3 with the key
+# (hdr bits 16-31); Requests and Replies stay untagged; WPaxos and M2Paxos add LeaderChange
+KEYED_TYPES = (T_P1A, T_P1B, T_P2A, T_P2B, T_P3, T_LEADERCHG)
 CLIENT = abi.CLIENT_SRC
 
 
@@ -297,12 +306,20 @@ class Replica:
         self.me, self.N, self.ids, self.quorums = me, sum(npz), ids_of(npz), Quorums(npz, cfg.fz)
         self.W, self.kv, self.ephemeral = cfg.window, bool(cfg.kv), bool(cfg.ephemeral_leader)
         self.client, self.command_of = client, command_of
-        self.paxos = Paxos(self, cfg.q1, cfg.q2, bool(cfg.thrifty), bool(cfg.reply_when_commit))
+        self.paxos = self.new_paxos(cfg)
         self.forwards = {}                                 # never cleaned (node.go:83-97, 165-172)
         self.data, self.version = {}, 0
         self.out = []
         self.sent = self.replies = self.discarded = self.client_requests = 0
         self.delivered = collections.Counter()
+
+    def new_paxos(self, cfg):
+        """The replica's single paxos.Paxos (paxos/replica.go:26); a per-key replica has none."""
+        return Paxos(self, cfg.q1, cfg.q2, bool(cfg.thrifty), bool(cfg.reply_when_commit))
+
+    def instances(self):
+        """{key: Paxos} of the instances this replica holds."""
+        return {0: self.paxos}
 
     # ---- socket.go
     def send(self, dst, *words):
@@ -429,12 +446,18 @@ class Client:
         self.due.remove((t, dst, cid))
 
 
-def words_of(recs):
+def words_of(recs, keys=0):
     """One traced message -> its words, after checking its framing: only a P1b carries payload
-    records, as many as its header says, each a P1B_ENTRY."""
+    records, as many as its header says, each a P1B_ENTRY.  Multi-Paxos (keys = 0) has no key tag
+    and no LeaderChange; of a per-key protocol's messages P1a..P3 and LeaderChange carry a key
+    below `keys`, Requests and Replies none."""
     hdr = recs[0][1]
     t, n = hdr & 0xFF, (hdr >> 8) & 0xFF
-    assert hdr >> 16 == 0 and t in SOCKET_TYPES and (n == 0 or t == T_P1B) and len(recs) == 1 + n, f"framing of {recs}"
+    if keys and t in KEYED_TYPES:
+        assert hdr >> 16 < keys, f"key tag of {recs}"
+    else:
+        assert hdr >> 16 == 0 and t in SOCKET_TYPES, f"header of {recs}"
+    assert (n == 0 or t == T_P1B) and len(recs) == 1 + n, f"framing of {recs}"
     assert all(r[1] == T_P1B_ENTRY for r in recs[1:]), f"payload of {recs}"
     return tuple(w for r in recs for w in r[1:])
 
@@ -448,17 +471,19 @@ def crash_windows(faults, gid):
 Replay = collections.namedtuple("Replay", "replicas unmatched matched delivered last_step panics client")
 
 
-def replay(msgs, cfg, wl, gid, command_of, crashes=(), injected=(), delivered_in=()):
+def replay(msgs, cfg, wl, gid, command_of, crashes=(), injected=(), delivered_in=(), make_replica=Replica):
     """One cluster's trace [(step, src, dst, [records])] through its model replicas.  Returns the
     replicas, the model's sends nobody received ({(src, dst): [(step, words)]}), the number of
     matched messages, the deliveries per type (P1B_ENTRY: payload entries), the last step with a
     record, the panics [(step, replica)] and the client.
     Inputs besides the trace: `crashes` [(replica, from, to)]; `injected` {(step, dst, cid)} of
-    paxisim_inject; `delivered_in` {(step, src, dst, words)} of paxisim_deliver."""
+    paxisim_inject; `delivered_in` {(step, src, dst, words)} of paxisim_deliver.  `make_replica`
+    (index, cfg, client, command_of) builds one model replica: `Replica`, or a per-key one."""
     N, D = abi.n_replicas(cfg), cfg.max_delay
+    keys = cfg.keys if cfg.protocol in abi.PER_KEY else 0
     kc = mix64(cfg.seed ^ mix64((gid + 0x9E3779B97F4A7C15) & M64)) & M32
     client = Client(wl)
-    reps = [Replica(r, cfg, client, command_of) for r in range(N)]
+    reps = [make_replica(r, cfg, client, command_of) for r in range(N)]
     sent = collections.defaultdict(list)          # (src, dst) -> [(step, words)] not yet received
     per = collections.defaultdict(lambda: collections.defaultdict(list))
     for (t, src, dst, recs) in msgs:
@@ -471,8 +496,12 @@ def replay(msgs, cfg, wl, gid, command_of, crashes=(), injected=(), delivered_in
         link = sent[(src, dst)]
         hit = [k for k, (te, w) in enumerate(link) if w == words and te < t]
         assert hit, f"step {t}: {src}->{dst} delivered {words}, which the model's {src} never sent"
-        te = link.pop(hit[0])[0]                   # the oldest: a link's equal messages are one multiset
-        assert t - te <= 1 + D, f"step {t}: {src}->{dst} {words} sent at step {te}"
+        # a link's equal messages are one multiset: the oldest that can still be on its way.  An older
+        # equal one (a LeaderChange repeats under an unchanged ballot) was lost and stays a leftover,
+        # which check_end holds against `dropped`.
+        young = [k for k in hit if t - link[k][0] <= 1 + D]
+        assert young, f"step {t}: {src}->{dst} {words} sent at step {link[hit[-1]][0]}"
+        link.pop(young[0])
         return 1
 
     for (t, dst) in sorted(per):
@@ -482,12 +511,12 @@ def replay(msgs, cfg, wl, gid, command_of, crashes=(), injected=(), delivered_in
         if any(r == dst and a <= t < b for (r, a, b) in crashes):        # socket.Recv discards (socket.go:111-118)
             for src in [s for s in by_src if s < N]:
                 for recs in by_src.pop(src):
-                    matched += match(t, src, dst, words_of(recs))
+                    matched += match(t, src, dst, words_of(recs, keys))
                     me.discarded += 1
         step_key = fmix32(kc ^ ((t * 0x9E3779B1) & M32))
         dead = False
         for src, recs in handled(step_key, dst, by_src, N + 1):
-            words = words_of(recs)
+            words = words_of(recs, keys)
             if src == N:
                 assert words[0] == T_REQUEST and words[1:3] == (0, 0), f"client record {recs}"
                 if (t, dst, words[3]) not in injected:
@@ -522,49 +551,95 @@ def ballot64(ids, b):
 OUTSIDE = abi.F_UNFAITHFUL | abi.F_MBOX_OVF | abi.F_PEND_OVF | abi.F_BALLOT_OVF
 
 
+def check_instance(sim, c, r, m, p, st, W, key=0):
+    """One paxos.Paxos `p` of model replica `m` against an instance record or a Multi-Paxos
+    replica state `st`, and its window against read_log."""
+    where = f"cluster {c} replica {r} key {key}"
+    got = (st.ballot, st.slot, st.execute, st.active, st.npending, bin(st.p1_acks).count("1"), st.digest)
+    want = (ballot64(m.ids, p.ballot), p.slot, p.execute, int(p.active), len(p.requests), len(p.quorum), p.digest)
+    assert got == want, f"{where}: (ballot, slot, execute, active, npending, |p1 quorum|, digest) {got} against {want}"
+    assert {k for k in range(m.N) if st.p1_acks >> k & 1} == p.quorum, f"{where}: phase-1 quorum"
+    for le in sim.read_log(c, r, p.execute, W, key=key):
+        e = p.log.get(le.slot)
+        assert le.flags & abi.LOG_HELD
+        if e is None:
+            assert not le.flags & abi.LOG_EXISTS, f"{where} slot {le.slot}: the model holds no entry"
+            continue
+        bits = abi.LOG_HELD | abi.LOG_EXISTS | (abi.LOG_COMMIT if e.commit else 0) | \
+            (abi.LOG_QUORUM if e.quorum is not None else 0) | (abi.LOG_REQUEST if e.request is not None else 0)
+        want = (ballot64(m.ids, e.ballot), e.command, bits, sum(1 << k for k in e.quorum or ()),
+                e.request.word() if e.request is not None else 0)
+        assert (le.ballot, le.cmd, le.flags, le.acks, le.request) == want, f"{where} slot {le.slot}"
+
+
+def check_keyed(sim, c, r, m, st, ins, cfg):
+    """A per-key replica: every (replica, key) record of read_instances against the instance map
+    and the policies, then read_state's aggregates over the instances as include/paxisim.h defines
+    them (ballot: the highest; slot: keys led, Replica.keys; execute, active, npending: sums;
+    p1_acks: the mask of existing instances; digest: mix64 chained over the key digests in key
+    order, 0 for a key without instance)."""
+    paxi, digest = m.instances(), 0
+    for k in range(cfg.keys):
+        i, p = ins[k], paxi.get(k)
+        assert i.exists == (p is not None), f"cluster {c} replica {r} key {k}: exists = {i.exists}"
+        if p is None:                                      # never initialised: nothing but the empty record
+            got = (i.ballot, i.slot, i.execute, i.active, i.p1_acks, i.npending, i.digest, tuple(i.policy_state))
+            assert got == (0, -1, 0, 0, 0, 0, 0, (0, 0, 0, 0)), f"cluster {c} replica {r} key {k}: {got}"
+            digest = mix64(digest)
+            continue
+        check_instance(sim, c, r, m, p, i, cfg.window, k)
+        for name, want in p.policy.expect().items():
+            got = getattr(i, name)
+            got = tuple(got[:len(want)]) if name == "policy_state" else got
+            assert got == want, f"cluster {c} replica {r} key {k}: {name} {got} against the model's {want}"
+        digest = mix64(digest ^ p.digest)
+    ps = list(paxi.values())
+    got = (st.ballot, st.slot, st.execute, st.active, st.p1_acks, st.npending, st.digest)
+    want = (ballot64(m.ids, max((p.ballot for p in ps), default=0)), sum(1 for p in ps if p.is_leader()),
+            sum(p.execute for p in ps), sum(p.active for p in ps), sum(1 << k for k in paxi),
+            sum(len(p.requests) for p in ps), digest)
+    assert got == want, f"cluster {c} replica {r}: (highest ballot, keys led, executed, active, exists mask, " \
+                        f"pending, digest chain) {got} against the model's {want}"
+
+
 def check_end(rp, sim, c, cfg, steps, drains):
-    """The end of a replayed cluster c against read_state / read_log of `sim`, and the sends nobody
-    received.  Returns the cluster's flag word."""
+    """The end of a replayed cluster c against read_state / read_log (a per-key protocol: and
+    read_instances) of `sim`, and the sends nobody received.  Returns the cluster's flag word."""
     N, W, D = len(rp.replicas), cfg.window, cfg.max_delay
+    keyed = cfg.protocol in abi.PER_KEY
     states = sim.read_state(c, 1)
+    ins = sim.read_instances(c, 1) if keyed else None
     word = 0
     for st in states:
         word |= st.flags
     assert not word & OUTSIDE, f"cluster {c} is flagged {word:#x}: outside the model's claim"
     dead = {r for (_, r) in rp.panics}
     for r, m in enumerate(rp.replicas):
-        st, p = states[r], m.paxos
+        st, ps = states[r], list(m.instances().values())
         assert bool(st.flags & abi.F_POISON) == (r in dead), f"cluster {c} replica {r}: POISON against {rp.panics}"
-        got = (st.ballot, st.slot, st.execute, st.active, st.npending, bin(st.p1_acks).count("1"), st.digest)
-        want = (ballot64(m.ids, p.ballot), p.slot, p.execute, int(p.active), len(p.requests), len(p.quorum), p.digest)
-        assert got == want, f"cluster {c} replica {r}: (ballot, slot, execute, active, npending, |p1 quorum|, digest)"
-        assert {k for k in range(N) if st.p1_acks >> k & 1} == p.quorum, f"cluster {c} replica {r}: phase-1 quorum"
+        if keyed:
+            check_keyed(sim, c, r, m, st, ins[r * cfg.keys:(r + 1) * cfg.keys], cfg)
+        else:
+            check_instance(sim, c, r, m, m.paxos, st, W)
         got = (st.commits, st.replies, st.executions, st.executed_writes, st.client_requests, st.sent, st.discarded)
-        want = (p.commits, m.replies, p.execute, m.version, m.client_requests, m.sent, m.discarded)
+        want = (sum(p.commits for p in ps), m.replies, sum(p.execute for p in ps), m.version, m.client_requests, m.sent,
+                m.discarded)
         assert got == want, f"cluster {c} replica {r}: (commits, replies, executions, executed_writes, " \
                             f"client_requests, sent, discarded) {got} against the model's {want}"
         assert {t: n for t, n in enumerate(st.delivered) if n} == dict(m.delivered), f"cluster {c} replica {r}: delivered"
-        for le in sim.read_log(c, r, p.execute, W):
-            e = p.log.get(le.slot)
-            assert le.flags & abi.LOG_HELD
-            if e is None:
-                assert not le.flags & abi.LOG_EXISTS, f"cluster {c} replica {r} slot {le.slot}: the model holds no entry"
-                continue
-            bits = abi.LOG_HELD | abi.LOG_EXISTS | (abi.LOG_COMMIT if e.commit else 0) | \
-                (abi.LOG_QUORUM if e.quorum is not None else 0) | (abi.LOG_REQUEST if e.request is not None else 0)
-            want = (ballot64(m.ids, e.ballot), e.command, bits, sum(1 << k for k in e.quorum or ()),
-                    e.request.word() if e.request is not None else 0)
-            assert (le.ballot, le.cmd, le.flags, le.acks, le.request) == want, f"cluster {c} replica {r} slot {le.slot}"
-        if any(s >= p.execute + W for s in p.log):
+        if any(s >= p.execute + W for p in ps for s in p.log):
             assert st.flags & abi.F_WOVF, f"cluster {c} replica {r}: an entry beyond the window, and no WOVF"
-        if any(s < p.execute for s in p.log):
+        if any(s < p.execute for p in ps for s in p.log):
             assert st.flags & abi.F_GHOST, f"cluster {c} replica {r}: an entry below execute, and no GHOST"
     left = [(te, k, w) for k, v in rp.unmatched.items() for (te, w) in v]
     if rp.panics:
+        # the cluster is frozen after the panic's step: the leftovers are held against `dropped` as
+        # those of a run of that many steps that does not drain
         assert rp.last_step <= rp.panics[0][0]
-        return word
-    due = [d for d in rp.client.due if d[0] < steps]
-    assert not due, f"cluster {c}: requests the model's client sent and the trace lacks: {sorted(due)[:3]}"
+        steps, drains = rp.panics[0][0] + 1, False
+    else:
+        due = [d for d in rp.client.due if d[0] < steps]
+        assert not due, f"cluster {c}: requests the model's client sent and the trace lacks: {sorted(due)[:3]}"
     dropped = sum(s.dropped for s in states)
     if drains:
         assert rp.last_step < steps - 1 - D, "the run has not drained"
@@ -577,7 +652,7 @@ def check_end(rp, sim, c, cfg, steps, drains):
     return word
 
 
-def replay_cluster(sim, sh, c, msgs, injected=(), delivered_in=()):
+def replay_cluster(sim, sh, c, msgs, injected=(), delivered_in=(), make_replica=Replica):
     """Replay traced cluster c of a finished run of shape `sh` on `sim` (the oracle or the device)
     and check its end.  Returns the Replay and the cluster's flag word."""
     cfg = sh.cfg
@@ -590,7 +665,7 @@ def replay_cluster(sim, sh, c, msgs, injected=(), delivered_in=()):
         return memo[cid]
 
     rp = replay(msgs, cfg, sh.wl, cfg.cluster_base + c, command_of, crash_windows(sh.faults, cfg.cluster_base + c),
-                injected, delivered_in)
+                injected, delivered_in, make_replica)
     return rp, check_end(rp, sim, c, cfg, sh.steps, sh.drains)
 
 
