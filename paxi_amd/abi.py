@@ -302,6 +302,10 @@ VERDICT_PROTOTYPES = {
 }
 
 
+# enum paxisim_unit (include/paxisim_shape.h): what Simulation.step_unit returns
+UNIT_GENERIC, UNIT_FIXED_PAXOS5 = 0, 1
+
+
 # C prototypes shared by the product library (prefix "paxisim") and the oracle ("oracle").
 def declare(lib, prefix):
     P = C.POINTER

@@ -45,6 +45,9 @@ struct Knobs {
   uint32_t pipe_slots = 0;        // PAXISIM_PIPE_SLOTS: cap on the persistent grid (0: none)
   uint32_t compact_every = 0;     // PAXISIM_COMPACT_EVERY: steps between compactions (0: unset)
   int pools = 0;                  // PAXISIM_POOLS: 0 unset, 1 or 2, -1 anything else (refused)
+  // PAXISIM_SHAPE: 1 (the default) lets a handle of the fixed shape run the unit compiled for it
+  // (shape_plan.h), 0 keeps every handle on the generic units (A/B); -1: anything else (refused)
+  int shape = 1;
   long long arena_pad_mb = 0;     // PAXISIM_ARENA_PAD_MB, PAXISIM_ARENA_CONTIG: arena placement
   bool arena_contig = false;      // experiments (the two run modes)
 };
@@ -71,6 +74,7 @@ inline Knobs knobs_from_env() {
   if (const char* e = getenv("PAXISIM_PIPE_SLOTS")) k.pipe_slots = (uint32_t)strtoul(e, nullptr, 0);
   if (const char* e = getenv("PAXISIM_COMPACT_EVERY")) k.compact_every = at_least_1(e);
   if (const char* e = getenv("PAXISIM_POOLS")) k.pools = !strcmp(e, "1") ? 1 : !strcmp(e, "2") ? 2 : -1;
+  if (const char* e = getenv("PAXISIM_SHAPE")) k.shape = !strcmp(e, "1") ? 1 : !strcmp(e, "0") ? 0 : -1;
   if (const char* e = getenv("PAXISIM_ARENA_PAD_MB")) k.arena_pad_mb = atoll(e);
   if (const char* e = getenv("PAXISIM_ARENA_CONTIG")) k.arena_contig = atoi(e) != 0;
   return k;
@@ -171,6 +175,7 @@ inline int check_config(const paxisim_config* cfg, const paxisim_workload* wl, c
   if (wl->distribution == PAXISIM_DIST_CONFLICT && wl->conflicts > 100) return fail(PAXISIM_EINVAL, "conflicts > 100");
   if (int rc = check_keys(cfg, wl)) return rc;
   if (!kn.serial_ok) return fail(PAXISIM_EINVAL, "PAXISIM_SERIAL must be 0 or 1");
+  if (kn.shape < 0) return fail(PAXISIM_EINVAL, "PAXISIM_SHAPE must be 0 or 1");
   for (uint32_t w = 0; w < wl->outstanding; w++)
     if (wl->target[w] >= N) return fail(PAXISIM_EINVAL, "target[%u]", w);
   if (fp->slow_ppm && (fp->slow_min > fp->slow_max || fp->slow_max > cfg->max_delay))

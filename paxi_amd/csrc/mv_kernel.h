@@ -35,7 +35,7 @@
 namespace pxs {
 
 __host__ __device__ inline size_t mv_row(const Params& P, uint32_t key, uint32_t r, uint64_t cl) {
-  return ((size_t)key * P.N + r) * P.C + cl;
+  return ((size_t)key * SH_N(P) + r) * P.C + cl;
 }
 
 // Replica r of local cluster cl puts value v to key (db.go:123-134).
@@ -72,10 +72,10 @@ __global__ void __launch_bounds__(MV_WAVES * 64) mv_consensus_kernel(Params P, u
   for (uint64_t p = wave; p < pairs; p += waves) {
     const uint32_t key = (uint32_t)(p / nc);
     const uint64_t cl = c0 + (p - (uint64_t)key * nc);
-    const uint32_t n = lane < P.N ? P.mv_cnt[mv_row(P, key, lane, cl)] : 0u;
+    const uint32_t n = lane < SH_N(P) ? P.mv_cnt[mv_row(P, key, lane, cl)] : 0u;
     const uint32_t kept = n < H ? n : H;
     uint32_t top = 0;
-    for (uint32_t r = 0; r < P.N; r++) {
+    for (uint32_t r = 0; r < SH_N(P); r++) {
       const uint32_t nr = __shfl(n, (int)r, 64), kr = __shfl(kept, (int)r, 64);
       versions += nr;
       dropped += nr - kr;

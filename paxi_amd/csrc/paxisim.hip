@@ -26,10 +26,12 @@
 #include "sim_core.h"
 #include "create_plan.h"
 #include "pool_plan.h"
+#include "shape_plan.h"
 #include "snapshot_kernel.h"
 #include "snapshot_plan.h"
 #include "step_ops.h"
 #include "verdict_kernel.h"
+#include "../../include/paxisim_shape.h"
 
 using namespace pxs;
 
@@ -69,6 +71,9 @@ struct paxisim {
   hipStream_t stream = nullptr;
   StepOps ops{};
   int lds_set = -1;                // dynamic-LDS ceiling set for ops on this handle's device
+  // the fixed-shape unit (k_paxos5f.hip): shape_fit: the handle has the shape in every
+  // field but the scripted-fault count, the one pinned field that changes after create; fixed: ops is that unit's
+  bool shape_fit = false, fixed = false;
   uint32_t t = 0;
   uint32_t S = 32;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
@@ -906,6 +911,35 @@ static StepOps lat_step_ops_for(uint32_t protocol, uint32_t N, bool wlds, bool s
   return pxs_lat::paxos_step_ops(N);
 }
 
+// The 5-replica Multi-Paxos serial unit compiled for config 2's fixed shape (k_paxos5f.hip, shape.h)
+// and its recording twin, again the declarations of step_ops.h under namespaces of their own.
+namespace pxs_fix {
+pxs::StepOps paxos5_fixed_step_ops();
+}
+namespace pxs_fix_lat {
+pxs::StepOps paxos5_fixed_step_ops();
+}
+
+// The step unit a handle runs: the fixed-shape one while the handle has the shape (shape_plan.h),
+// else the generic one of its protocol and N; the recording build of either once latency is enabled.
+// Both units keep the same state in the same layout and take the same launch shape, so a handle
+// changes unit between two launches with nothing to convert.
+static ShapeFields shape_fields(const Params& P) {
+  return ShapeFields{P.N, P.NS, P.NI, P.NK, P.Z, P.W, P.q1, P.q2, P.kv, P.dist, P.rwc, P.thrifty, P.ephemeral,
+                     P.nfaults, P.late_workers, P.max_requests, P.locality_ppm, P.move_every, P.key_tail};
+}
+static void select_unit(paxisim* h) {
+  const bool serial = h->ops.serial;
+  const bool fixed = h->shape_fit && serial && shape_fields_fit(shape_fields(h->P));
+  const bool lat = h->P.lat_bins != 0;
+  StepOps ops = fixed ? (lat ? pxs_fix_lat::paxos5_fixed_step_ops() : pxs_fix::paxos5_fixed_step_ops())
+                      : (lat ? lat_step_ops_for(h->P.protocol, h->P.N, h->P.wlds != 0, serial)
+                             : step_ops_for(h->P.protocol, h->P.N, h->P.wlds != 0, serial));
+  h->ops = ops;
+  h->fixed = fixed;
+  h->lds_set = -1;   // the dynamic-LDS ceiling is per kernel
+}
+
 static hipError_t ensure_lds(paxisim* h);
 
 static size_t count_blocks(size_t slots) { return (slots + CB - 1) / CB; }
@@ -1044,6 +1078,10 @@ static int create_on_device(paxisim* h, const Knobs& kn, uint32_t variant, uint3
   h->cmp_every = sc.cmp_every;
   h->pipe_slots = kn.pipe_slots;
   if (const int rc = pools_setup(h, kn)) return rc;
+  // the plan stands: a handle of the fixed shape takes the unit compiled for it (same layout, same
+  // launch shape; the scripted faults of a handle being created are none yet)
+  h->shape_fit = !(shape_misfit(cfg, &h->wl, 0u, ShapeKnobs{kn.serial, kn.shape}, P.packed != 0) & ~SHAPE_NFAULTS);
+  if (h->shape_fit) select_unit(h);
 
   // every pool's bound: the clusters of its region
   uint32_t b0 = (uint32_t)cfg->clusters;
@@ -1105,6 +1143,13 @@ extern "C" int paxisim_fault_add(paxisim* h, const paxisim_fault* f) {
                         hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   h->P.nfaults = (uint32_t)h->faults.size();
+  if (h->fixed) select_unit(h);   // a scripted fault leaves the fixed shape: the generic unit from the next launch on
+  return 0;
+}
+
+extern "C" int paxisim_step_unit(paxisim* h, uint32_t* unit) {
+  if (!h || !unit) return fail(PAXISIM_EINVAL, "null argument");
+  *unit = h->fixed ? PAXISIM_UNIT_FIXED_PAXOS5 : PAXISIM_UNIT_GENERIC;
   return 0;
 }
 
@@ -1679,6 +1724,7 @@ extern "C" int paxisim_latency_enable(paxisim* h, uint32_t bins) {
   h->P = P;
   h->ops = ops;
   h->lds_set = -1;        // the dynamic-LDS ceiling is per kernel
+  if (h->fixed) select_unit(h);   // the recording twin of the fixed-shape unit
   h->d_lat_out = o;
   h->lat_bytes = sb + ab + ob;
   return 0;
@@ -2525,6 +2571,7 @@ extern "C" int paxisim_restore(paxisim* h, const void* buf, uint64_t bytes) {
   if (e != hipSuccess) return fail(PAXISIM_EDEVICE, "restore: %s (the handle's state is undefined)", hipGetErrorString(e));
   h->faults.swap(faults);
   P.nfaults = H.n_faults;
+  if (h->shape_fit) select_unit(h);   // the unit follows the restored fault count (either way)
   h->t = H.step;
   for (uint32_t p = 0; p < h->npools; p++) h->pool[p].last_cmp = last_cmp[p];
   return 0;
@@ -2605,6 +2652,7 @@ extern "C" int paxisim_fork(paxisim* h, paxisim** out) {
   if (e != hipSuccess) return drop(fail(PAXISIM_EDEVICE, "fork: %s", hipGetErrorString(e)));
   f->faults = h->faults;
   f->P.nfaults = P.nfaults;
+  if (f->shape_fit) select_unit(f);
   f->t = h->t;
   for (uint32_t p = 0; p < h->npools; p++) f->pool[p].last_cmp = h->pool[p].last_cmp;
   if (f->npools > 1) f->main_ahead = true;   // the pools' streams wait for these copies

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "../../include/paxisim.h"
+#include "shape.h"
 
 // PXS_LAT = 1 builds a kernel unit that records client request latency
 // (lat_kernel.h).  Every k_*.hip unit is built twice (__graft_entry__.LAT_FLAGS):
@@ -27,7 +28,13 @@
 #ifndef PXS_LAT
 #define PXS_LAT 0
 #endif
-#if PXS_LAT
+// PXS_SHAPE = 1 builds a unit for one fixed config shape (shape.h); its instances live in
+// namespaces of their own in the same way, beside the generic units' (k_paxos5f.hip).
+#if PXS_LAT && PXS_SHAPE
+#define pxs pxs_fix_lat
+#elif PXS_SHAPE
+#define pxs pxs_fix
+#elif PXS_LAT
 #define pxs pxs_lat
 #endif
 
@@ -270,12 +277,12 @@ constexpr uint32_t WP_WORDS = 5;
 #define PXS_WP_LANEMAJOR 0
 #endif
 __device__ __forceinline__ size_t wp_si(const Params& P, uint64_t blk, uint32_t k, uint32_t r, uint32_t lane) {
-  if (PXS_WP_LANEMAJOR) return ((blk * P.N + r) * 64u + lane) * P.keys + k;
-  return ((blk * P.keys + k) * P.N + r) * 64u + lane;
+  if (PXS_WP_LANEMAJOR) return ((blk * SH_N(P) + r) * 64u + lane) * P.keys + k;
+  return ((blk * P.keys + k) * SH_N(P) + r) * 64u + lane;
 }
 __device__ __forceinline__ uint32_t* wp_img(const Params& P, uint64_t blk, uint32_t k, uint32_t r, uint32_t lane) {
   return reinterpret_cast<uint32_t*>(P.image + (size_t)blk * P.img.bytes + P.img.off_a) +
-         ((size_t)(k * P.N + r) * WP_WORDS << 6) + lane;
+         ((size_t)(k * SH_N(P) + r) * WP_WORDS << 6) + lane;
 }
 __device__ __forceinline__ void wp_read(const Params& P, uint64_t blk, uint32_t k, uint32_t r, uint32_t lane, uint4& a,
                                         uint4& b) {
@@ -376,7 +383,7 @@ __host__ __device__ __forceinline__ bool quorum_check(uint32_t kind, uint32_t N,
   return false;
 }
 __device__ __forceinline__ bool quorum_ok(const Params& P, uint32_t kind, uint32_t mask) {
-  return quorum_check(kind, P.N, P.Z, P.npz, P.zmask, P.fz, mask);
+  return quorum_check(kind, SH_N(P), SH_Z(P), P.npz, P.zmask, P.fz, mask);
 }
 
 // ---- loads retired on the spot ----------------------------------------------
@@ -405,7 +412,7 @@ __device__ __forceinline__ uint4 ldg(const uint4* p) {
 __device__ __forceinline__ bool scripted(const Params& P, uint32_t kind, uint64_t gid, uint32_t src,
                                          uint32_t dst, uint32_t t, uint32_t* param) {
   bool hit = false;
-  for (uint32_t i = 0; i < P.nfaults; i++) {
+  for (uint32_t i = 0; i < SH_nfaults(P); i++) {
     paxisim_fault f;
     {
       const uint4 a = ldg(&P.faults[i].a);
@@ -479,7 +486,7 @@ __device__ __forceinline__ void stamp_case(const Params& P, uint32_t blk, uint32
 // ---- SoA addressing --------------------------------------------------------
 __device__ __forceinline__ size_t rc(const Params& P, uint32_t r, uint64_t c) { return (size_t)r * P.C + c; }
 __device__ __forceinline__ size_t krc(const Params& P, uint32_t k, uint32_t r, uint64_t c) {
-  return ((size_t)k * P.N + r) * P.C + c;
+  return ((size_t)k * SH_N(P) + r) * P.C + c;
 }
 
 // ---- diagnostic build (PXS_TALLY): the HBM requests of each

@@ -53,7 +53,7 @@ struct Ent { uint32_t b, c, a; };
 // at the kernel's entry), so these branches fold.
 template <int NT>
 __device__ __forceinline__ uint32_t eidx(const Params& P, const Rep<NT>& x, int32_t s) {
-  return x.e0 + ((uint32_t)s & (P.W - 1u)) * x.es;
+  return x.e0 + ((uint32_t)s & (SH_W(P) - 1u)) * x.es;
 }
 template <int NT>
 __device__ __forceinline__ bool packed_log(const Rep<NT>& x) { return x.es != LANES; }
@@ -116,7 +116,7 @@ __device__ __forceinline__ void cm_note(Rep<NT>& x, uint32_t i, uint32_t c) {
 // the window's exists / committed bits describe its slots (the packed Multi-Paxos units, W <= 16)
 template <int NT>
 __device__ __forceinline__ bool win_bits(const Params& P, const Rep<NT>& x) {
-  return packed_log(x) && !per_key(x) && P.W <= 16u;
+  return packed_log(x) && !per_key(x) && SH_W(P) <= 16u;
 }
 template <int NT>
 __device__ __forceinline__ void set_b(Rep<NT>& x, uint32_t i, uint32_t v) {
@@ -323,7 +323,7 @@ __device__ __forceinline__ void raise_win(Rep<NT>& x, uint32_t f) {
 // serial (ldg): eight in flight at once would cost 32 registers.
 template <int NT>
 __device__ __forceinline__ uint4* gref(const Params& P, const Rep<NT>& x, uint32_t g) {
-  uint4* q = per_key(x) ? &P.gst[((size_t)x.inst * P.C + x.c) * GMAX + g] : &P.gst[((size_t)g * P.NI + x.inst) * P.C + x.c];
+  uint4* q = per_key(x) ? &P.gst[((size_t)x.inst * P.C + x.c) * GMAX + g] : &P.gst[((size_t)g * SH_NI(P) + x.inst) * P.C + x.c];
   PXS_TALLY_AT(P, x.blk, TC_GHOST, q, false);   // (every use of a ghost reference counted as a line)
   return q;
 }
@@ -400,7 +400,7 @@ __device__ __forceinline__ void ghost_p2b(const Params& P, Rep<NT>& x, int32_t m
 #endif
 template <int NT>
 __device__ __forceinline__ bool in_window(const Params& P, const Rep<NT>& x, int32_t s) {
-  return s >= x.execute && s < x.execute + (int32_t)P.W;
+  return s >= x.execute && s < x.execute + (int32_t)SH_W(P);
 }
 
 template <int NT>
@@ -432,7 +432,7 @@ __device__ __forceinline__ void paxos_p2a(const Params& P, Rep<NT>& x, uint32_t 
   } else {
     raise_win(x, PAXISIM_F_WOVF | PAXISIM_F_UNFAITHFUL);
   }
-  if (P.thrifty) {                                   // MulticastQuorum(N/2+1) (socket.go:132-145), ring order
+  if (SH_thrifty(P)) {                                   // MulticastQuorum(N/2+1) (socket.go:132-145), ring order
     const uint32_t N = nrep<NT>(P);
     uint32_t sent = 0;
     intent_flush<NT>(P, x);
@@ -461,7 +461,7 @@ __device__ __forceinline__ void paxos_handle_request(const Params& P, Rep<NT>& x
 template <int NT>
 __device__ __forceinline__ void handle_request(const Params& P, Rep<NT>& x, uint32_t req) {  // replica.go:42-66
   const bool leader = x.active || bal_id(x.ballot) == x.r;
-  if (P.ephemeral || leader || x.ballot == 0) paxos_handle_request<NT>(P, x, req);
+  if (SH_ephemeral(P) || leader || x.ballot == 0) paxos_handle_request<NT>(P, x, req);
   else node_forward<NT>(P, x, bal_id(x.ballot), req);
 }
 
@@ -526,7 +526,7 @@ __device__ __forceinline__ void paxos_exec(const Params& P, Rep<NT>& x, uint32_t
   uint32_t ni = ~0u, nc = 0u;                                      // the next slot's flags, loaded ahead
   for (;;) {
     if (packed_log(x)) {                                           // skip the HBM read of an uncommitted entry
-      if (P.W <= 16u ? !((x.cmask >> ((uint32_t)x.execute & (P.W - 1u))) & 1u) : x.execute > x.slot) break;
+      if (SH_W(P) <= 16u ? !((x.cmask >> ((uint32_t)x.execute & (SH_W(P) - 1u))) & 1u) : x.execute > x.slot) break;
     }
     const uint32_t i = eidx<NT>(P, x, x.execute);
     const uint32_t c = i == hi ? hc : (i == ni ? nc : eb(x, i));
@@ -539,18 +539,18 @@ __device__ __forceinline__ void paxos_exec(const Params& P, Rep<NT>& x, uint32_t
     if (x.iflags & PAXISIM_F_WOVF) x.flags |= PAXISIM_F_UNFAITHFUL;
     digest_need<NT>(P, x);
     const uint32_t cmd = c & CMD_MASK;
-    const uint32_t h = P.kv ? wl_hash(x.kc, cmd) : 0u;
-    const uint32_t key = P.kv ? kv_key<NT>(P, x, h, cmd) : 0u;
+    const uint32_t h = SH_kv(P) ? wl_hash(x.kc, cmd) : 0u;
+    const uint32_t key = SH_kv(P) ? kv_key<NT>(P, x, h, cmd) : 0u;
     if (c & (EF_REQSELF | EF_REQEXT))                             // Reply{Value: p.Execute(cmd)}, paxos.go:352-362
-      request_reply<NT>(P, x, ereq<NT>(P, x, i, c), cmd, P.kv ? kv_get<NT>(P, x, key) : 0u);
+      request_reply<NT>(P, x, ereq<NT>(P, x, i, c), cmd, SH_kv(P) ? kv_get<NT>(P, x, key) : 0u);
     x.digest = mix64(x.digest ^ (((uint64_t)(uint32_t)x.execute << 32) | cmd));
     x.dig_st = 2u;
-    if (P.kv) kv_exec<NT>(P, x, h, key, cmd);                      // p.Execute(e.command), paxos.go:352
+    if (SH_kv(P)) kv_exec<NT>(P, x, h, key, cmd);                      // p.Execute(e.command), paxos.go:352
     set_b(x, i, 0u);                                               // delete(p.log, execute)
     x.execute++;
     if ((uint32_t)x.execute % CKI == 0) {
       const uint32_t k = ((uint32_t)x.execute / CKI) % CKR;
-      const size_t ci = ((size_t)k * P.NI + x.inst) * P.C + x.c;
+      const size_t ci = ((size_t)k * SH_NI(P) + x.inst) * P.C + x.c;
       PXS_TALLY_AT(P, x.blk, TC_CKPT, &P.ck_e[ci], true);
       PXS_TALLY_AT(P, x.blk, TC_CKPT, &P.ck_d[ci], true);
       P.ck_e[ci] = (uint32_t)x.execute;
@@ -569,7 +569,7 @@ __device__ __forceinline__ void paxos_handle_p1a(const Params& P, Rep<NT>& x, ui
   }
   if (x.iflags & PAXISIM_F_WOVF) x.flags |= PAXISIM_F_UNFAITHFUL;
   int32_t hi = x.slot;
-  if (hi > x.execute + (int32_t)P.W - 1) hi = x.execute + (int32_t)P.W - 1;
+  if (hi > x.execute + (int32_t)SH_W(P) - 1) hi = x.execute + (int32_t)SH_W(P) - 1;
   uint32_t n = 0;
   for (int32_t s = x.execute; s <= hi; s++) {
     const uint32_t c = eb(x, eidx<NT>(P, x, s));
@@ -624,11 +624,11 @@ __device__ __forceinline__ void paxos_handle_p1b(const Params& P, Rep<NT>& x, ui
   }
   if (bal_id(mb) == x.r && mb == x.ballot) {
     x.p1mask |= 1u << src;
-    if (quorum_ok(P, P.q1, x.p1mask)) {
+    if (quorum_ok(P, SH_q1(P), x.p1mask)) {
       x.active = 1;
       if (x.iflags & PAXISIM_F_WOVF) x.flags |= PAXISIM_F_UNFAITHFUL;
       int32_t hi = x.slot;
-      if (hi > x.execute + (int32_t)P.W - 1) hi = x.execute + (int32_t)P.W - 1;
+      if (hi > x.execute + (int32_t)SH_W(P) - 1) hi = x.execute + (int32_t)SH_W(P) - 1;
       for (int32_t s = x.execute; s <= hi; s++) {
         const uint32_t i = eidx<NT>(P, x, s);
         const uint32_t c = eb(x, i);
@@ -657,7 +657,7 @@ __device__ __forceinline__ void paxos_handle_p2a(const Params& P, Rep<NT>& x, ui
       const uint32_t i = eidx<NT>(P, x, ms);
       // a slot whose exists bit is clear holds nothing the new entry keeps: no read
       Ent e{0u, 0u, 0u};
-      if (!win_bits<NT>(P, x) || ((x.cmask >> (16u + ((uint32_t)ms & (P.W - 1u)))) & 1u)) e = eget<NT>(x, i);
+      if (!win_bits<NT>(P, x) || ((x.cmask >> (16u + ((uint32_t)ms & (SH_W(P) - 1u)))) & 1u)) e = eget<NT>(x, i);
       if (e.c & EF_EXISTS) {
         if (!(e.c & EF_COMMIT) && mb > e.b) {
           if ((e.c & CMD_MASK) != mcid && (e.c & (EF_REQSELF | EF_REQEXT))) {
@@ -710,11 +710,11 @@ __device__ __forceinline__ void paxos_handle_p2b(const Params& P, Rep<NT>& x, ui
     const uint32_t ack = (PXS_P2B_EAGER ? ea0 : ec(x, i)) | (1u << src);
     set_c(x, i, ack);
     PXS_SUB_T1(pxs_a0, 11)
-    if (quorum_ok(P, P.q2, ack)) {
+    if (quorum_ok(P, SH_q2(P), ack)) {
       set_b(x, i, c | EF_COMMIT);
       x.commits++;
       post_broadcast<NT>(P, x, PAXISIM_MSG_P3 | x.ktag, mb, (uint32_t)ms, c & CMD_MASK);
-      if (P.rwc) {
+      if (SH_rwc(P)) {
         const uint32_t q = ereq<NT>(P, x, i, c);
         if (!q) { x.flags |= PAXISIM_F_POISON; x.stop = true; return; }   // nil r.Reply
         request_reply<NT>(P, x, q, req_cid(q), 0u);   // Reply{Command}: no Value
@@ -737,7 +737,7 @@ __device__ __forceinline__ void paxos_handle_p3(const Params& P, Rep<NT>& x, uin
     if (win_bits<NT>(P, x) && !(x.iflags & IF_REQST)) {
       // no entry here ever held a request or a quorum object: the slot's two bits are its
       // flags, and its old command is overwritten whatever it was - no read
-      const uint32_t m = x.cmask >> ((uint32_t)ms & (P.W - 1u));
+      const uint32_t m = x.cmask >> ((uint32_t)ms & (SH_W(P) - 1u));
       c = (m & 0x10000u ? EF_EXISTS : 0u) | (m & 1u ? EF_COMMIT : 0u);
     } else {
       c = eb(x, i);
@@ -754,7 +754,7 @@ __device__ __forceinline__ void paxos_handle_p3(const Params& P, Rep<NT>& x, uin
     }
     c = eset_cmd<NT>(P, x, i, c, mcid) | EF_COMMIT;
     set_b(x, i, c);
-    if (P.rwc) {
+    if (SH_rwc(P)) {
       if (c & (EF_REQSELF | EF_REQEXT)) {
         const uint32_t q = ereq<NT>(P, x, i, c);
         request_reply<NT>(P, x, q, req_cid(q), 0u);   // Reply{Command}: no Value
@@ -770,7 +770,7 @@ __device__ __forceinline__ void paxos_handle_p3(const Params& P, Rep<NT>& x, uin
   } else {
     raise_win(x, PAXISIM_F_WOVF);
   }
-  if (!P.rwc) paxos_exec<NT>(P, x);
+  if (!SH_rwc(P)) paxos_exec<NT>(P, x);
 }
 
 // HandleP2b (paxos.go:270-310) for a P2b that neither completes a quorum nor
@@ -793,7 +793,7 @@ __device__ __forceinline__ bool p2b_absorb(const Params& P, Rep<NT>& x, uint32_t
   if (bal_id(mb) == x.r && mb == eb0) {
     if (!(c & EF_QUORUM)) return false;                 // nil quorum: the full handler poisons
     const uint32_t ack = (PXS_P2B_EAGER ? ea0 : ec(x, i)) | (1u << src);
-    if (quorum_ok(P, P.q2, ack)) return false;          // commit: the full handler
+    if (quorum_ok(P, SH_q2(P), ack)) return false;          // commit: the full handler
     set_c(x, i, ack);
   }
   if (mb > x.ballot) {
@@ -839,15 +839,15 @@ struct PaxosProto {
     x.inst = x.r;
     x.key = 0;
     x.ktag = 0;
-    x.e0 = ((x.r * P.W) << 6) | x.lane;
+    x.e0 = ((x.r * SH_W(P)) << 6) | x.lane;
     if (packed_log(x)) {               // 16-B entries of the tile's array, a row of 64 per (replica, slot)
       x.e0 *= 4u;
-      x.l_a = reinterpret_cast<uint32_t*>(P.plog + (size_t)x.blk * (P.N * P.W * LANES));
+      x.l_a = reinterpret_cast<uint32_t*>(P.plog + (size_t)x.blk * (SH_N(P) * SH_W(P) * LANES));
     } else {
-      x.reqx = P.reqx + (size_t)x.blk * (P.N * P.W * LANES);
+      x.reqx = P.reqx + (size_t)x.blk * (SH_N(P) * SH_W(P) * LANES);
     }
     x.pend = P.pend + i;
-    x.pstride = P.NI * (uint32_t)P.C;
+    x.pstride = SH_NI(P) * (uint32_t)P.C;
   }
   template <int NT>
   __device__ static __forceinline__ void store(const Params& P, const Rep<NT>& x) {

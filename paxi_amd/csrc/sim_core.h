@@ -67,7 +67,7 @@ struct Rep {
 };
 
 template <int NT>
-__device__ __forceinline__ uint32_t nrep(const Params& P) { return NT ? (uint32_t)NT : P.N; }
+__device__ __forceinline__ uint32_t nrep(const Params& P) { return NT ? (uint32_t)NT : SH_N(P); }
 
 // delivered-by-type counters: 16 bits each, two per register (a launch's
 // steps are capped so that no count can reach 2^16, paxisim.hip)
@@ -126,7 +126,7 @@ __device__ __forceinline__ bool send_begin(const Params& P, Rep<NT>& x, uint32_t
     // whose bucket is never written
     uint32_t b = x.b0 + 1u + (uint32_t)((x.dly >> (4u * (to & 15u))) & 15u);
     if (b >= P.D) b -= P.D;
-    const uint32_t box = (b * nrep<NT>(P) + (ok ? to : 0u)) * P.NS + x.r;
+    const uint32_t box = (b * nrep<NT>(P) + (ok ? to : 0u)) * SH_NS(P) + x.r;
     const uint32_t k = ok ? (uint32_t)x.l_cnt[(box << 6) | x.lane] : 0u;
     const bool ovf = ok && k + nrec > P.M;
     if (ovf) x.flags |= PAXISIM_F_MBOX_OVF | PAXISIM_F_UNFAITHFUL;
@@ -145,7 +145,7 @@ __device__ __forceinline__ bool send_begin(const Params& P, Rep<NT>& x, uint32_t
   }
   uint32_t b = x.b0 + 1u + (uint32_t)((x.dly >> (4u * to)) & 15u);   // slow (socket.go:99-106)
   if (b >= P.D) b -= P.D;
-  const uint32_t box = (b * nrep<NT>(P) + to) * P.NS + x.r;
+  const uint32_t box = (b * nrep<NT>(P) + to) * SH_NS(P) + x.r;
   uint8_t* cp = &x.l_cnt[(box << 6) | x.lane];
   const uint32_t k = *cp;
   if (k + nrec > P.M) {
@@ -172,7 +172,7 @@ template <int NT>
 __device__ __forceinline__ ScriptedStep scripted_scan(const Params& P, const Rep<NT>& x) {
   ScriptedStep o = {0u, 0u, 0ull, false};
   const uint32_t N = nrep<NT>(P);
-  for (uint32_t i = 0; i < P.nfaults; i++) {
+  for (uint32_t i = 0; i < SH_nfaults(P); i++) {
     const uint4 a = P.faults[i].a;                                // kind, src, dst, param
     const uint4 b = P.faults[i].b;                                // cluster_lo, cluster_hi
     const uint4 c = P.faults[i].c;                                // step_from, step_to
@@ -271,7 +271,7 @@ __device__ __forceinline__ void intent_flush(const Params& P, Rep<NT>& x) {
       }
       uint32_t b = x.b0 + 1u + (uint32_t)((x.dly >> (4u * d)) & 15u);
       if (b >= P.D) b -= P.D;
-      const uint32_t box = (b * NU + d) * P.NS + x.r;
+      const uint32_t box = (b * NU + d) * SH_NS(P) + x.r;
       const uint32_t k = x.l_cnt[(box << 6) | x.lane];
       if (k + 1u > P.M) {
         x.flags |= PAXISIM_F_MBOX_OVF | PAXISIM_F_UNFAITHFUL;
@@ -295,7 +295,7 @@ __device__ __forceinline__ void intent_flush(const Params& P, Rep<NT>& x) {
     if (d < nrep<NT>(P) && ((x.im >> d) & 1u)) {
       uint32_t b = x.b0 + 1u + (uint32_t)((x.dly >> (4u * d)) & 15u);
       if (b >= P.D) b -= P.D;
-      box[d] = (b * nrep<NT>(P) + d) * P.NS + x.r;
+      box[d] = (b * nrep<NT>(P) + d) * SH_NS(P) + x.r;
       k[d] = x.l_cnt[(box[d] << 6) | x.lane];
     }
   }
@@ -364,7 +364,7 @@ __device__ __forceinline__ uint32_t mod_magic(uint32_t x, uint32_t d, uint32_t m
 // past the last table the Mu sequence repeats from move_loop.  Upper bound by
 // binary search: the number of thresholds <= u.
 __device__ __forceinline__ uint32_t wl_key_moving(const Params& P, uint32_t u, uint32_t cid) {
-  uint32_t e = (cid - 1u) / P.move_every;
+  uint32_t e = (cid - 1u) / SH_move_every_div(P);
   if (e >= P.move_tables) e = P.move_loop + (e - P.move_loop) % (P.move_tables - P.move_loop);
   const uint32_t* t = P.move_cdf + (size_t)e * PAXISIM_MAX_KEYS;
   uint32_t lo = 0, hi = P.keys - 1u;
@@ -379,19 +379,19 @@ __device__ __forceinline__ uint32_t wl_key_moving(const Params& P, uint32_t u, u
 // keys for a table draw beyond the key space (the unbounded "exponential"
 // tail; key_fit flags it where the key is used).
 __device__ __forceinline__ uint32_t wl_key_h(const Params& P, uint32_t h, uint32_t cid) {
-  if (P.locality_ppm) {
+  if (SH_locality_ppm(P)) {
     const uint32_t w = mod_magic(cid - 1u, P.WK, P.wk_magic);        // (cid-1) % WK
     const uint32_t z = P.wzone[w], nk = P.wnk[w];                    // zone_of[target[w]], its key count
-    if (nk && ppm_hit(fmix32(h ^ 0x165667B1u), P.locality_ppm)) return z + P.Z * mod_magic(h, nk, P.wnk_magic[w]);
+    if (nk && ppm_hit(fmix32(h ^ 0x165667B1u), SH_locality_ppm(P))) return z + SH_Z(P) * mod_magic(h, nk, P.wnk_magic[w]);
   }
-  switch (P.dist) {   // Bconfig.Distribution (benchmark.go:202-233), DESIGN.md §3.8
+  switch (SH_dist(P)) {   // Bconfig.Distribution (benchmark.go:202-233), DESIGN.md §3.8
     case PAXISIM_DIST_ORDER: return mod_magic(cid, P.kspace, P.kspace_magic);
     case PAXISIM_DIST_CONFLICT:   // Go's literal key 0 (benchmark.go:213-214), else the order counter + Min
       return fmix32(h ^ 0x3C6EF372u) % 100u < P.conflicts ? P.conflict_key : mod_magic(cid, P.kspace, P.kspace_magic);
     case PAXISIM_DIST_TABLE: {   // inverse CDF; the table index is uniform, so these are scalar loads
       const uint32_t u = fmix32(h ^ 0x2545F491u);
-      if (P.move_every) return wl_key_moving(P, u, cid);
-      if (P.key_tail && u >= P.key_tail) return P.keys;
+      if (SH_move_every(P)) return wl_key_moving(P, u, cid);
+      if (SH_key_tail(P) && u >= SH_key_tail(P)) return P.keys;
       uint32_t k = 0;
       for (uint32_t i = 0; i + 1u < P.keys; i++) k += u >= P.key_cdf[i] ? 1u : 0u;
       return k;
@@ -415,8 +415,8 @@ __device__ __forceinline__ uint32_t key_fit(const Params& P, Rep<NT>& x, uint32_
 }
 // The key value the reference's Database sees for index k (paxisim.h)
 __device__ __forceinline__ uint32_t key_value(const Params& P, uint32_t k) {
-  if (P.dist == PAXISIM_DIST_TABLE) return k;
-  if (P.dist == PAXISIM_DIST_CONFLICT && P.key_min && k == P.conflict_key) return 0u;
+  if (SH_dist(P) == PAXISIM_DIST_TABLE) return k;
+  if (SH_dist(P) == PAXISIM_DIST_CONFLICT && P.key_min && k == P.conflict_key) return 0u;
   return P.key_min + k;
 }
 __device__ __forceinline__ bool wl_write_h(const Params& P, uint32_t h) {
@@ -465,7 +465,7 @@ __device__ __forceinline__ void client_reply(const Params& P, Rep<NT>& x, uint32
     P.wrep[(size_t)w * P.C + x.c] = value;
   }
   const uint32_t issued = x.l_wiss[wi];
-  if (P.max_requests == 0 || issued < P.max_requests) {
+  if (SH_max_requests(P) == 0 || issued < SH_max_requests(P)) {
     const uint64_t nc = 1ull + w + (uint64_t)P.WK * issued;
     if (nc > CMD_MASK) {
       x.flags |= PAXISIM_F_PEND_OVF | PAXISIM_F_UNFAITHFUL;
@@ -477,7 +477,7 @@ __device__ __forceinline__ void client_reply(const Params& P, Rep<NT>& x, uint32
     if (PXS_LAT) lat_issue(P, w, x.c, x.t);
     uint32_t b = x.b0 + 1u;
     if (b >= P.D) b -= P.D;
-    const uint32_t box = (b * nrep<NT>(P) + P.target[w]) * P.NS + nrep<NT>(P);
+    const uint32_t box = (b * nrep<NT>(P) + P.target[w]) * SH_NS(P) + nrep<NT>(P);
     uint8_t* cp = &x.l_cnt[(box << 6) | x.lane];
     const uint32_t k = *cp;
     if (k >= P.M) {
@@ -496,14 +496,14 @@ __device__ __forceinline__ void client_reply(const Params& P, Rep<NT>& x, uint32
 // now (paxisim_workload.start_step), behind the requests already queued there.
 template <int NT>
 __device__ __forceinline__ void client_start(const Params& P, Rep<NT>& x) {
-  for (uint32_t m = P.late_workers; m; m &= m - 1u) {   // scalar loop: the mask is uniform
+  for (uint32_t m = SH_late_workers(P); m; m &= m - 1u) {   // scalar loop: the mask is uniform
     const uint32_t w = (uint32_t)__builtin_ctz(m);
     if (P.start_step[w] != x.t || P.target[w] != x.r) continue;
     const uint32_t wi = (w << 6) | x.lane;
     x.l_wcur[wi] = 1u + w;
     x.l_wiss[wi] = 1u;
     if (PXS_LAT) lat_issue(P, w, x.c, x.t);
-    const uint32_t box = (x.b0 * nrep<NT>(P) + x.r) * P.NS + nrep<NT>(P);
+    const uint32_t box = (x.b0 * nrep<NT>(P) + x.r) * SH_NS(P) + nrep<NT>(P);
     uint8_t* cp = &x.l_cnt[(box << 6) | x.lane];
     const uint32_t k = *cp;
     if (k >= P.M) {
@@ -633,8 +633,8 @@ __device__ __forceinline__ void replica_step(const Params& P, Rep<NT>& x
   x.im = 0;
   x.rw = 0;
   x.hs = step_key(x.kc, x.t);
-  if (P.late_workers) client_start<NT>(P, x);
-  const ScriptedStep sc = P.nfaults ? scripted_scan<NT>(P, x) : ScriptedStep{0u, 0u, 0ull, false};
+  if (SH_late_workers(P)) client_start<NT>(P, x);
+  const ScriptedStep sc = SH_nfaults(P) ? scripted_scan<NT>(P, x) : ScriptedStep{0u, 0u, 0ull, false};
   x.crashed = sc.crash;
   // The random fault process and the step's link masks.  Nothing before the
   // first handler's sends reads them, so the unstaged loop runs this after it
@@ -981,7 +981,7 @@ __device__ __forceinline__ void agree_drain(const Params& P, const Rep<NT>& x, u
       // (paxisim.hip swap_slots).  Only Multi-Paxos compacts; elsewhere slot ==
       // cluster and the slot index is used as before
       const uint64_t cl = Proto::kind == PAXISIM_PAXOS && !PXS_AGR_SLOT ? x.gid - P.cluster_base : x.c;
-      unsigned long long* a = &P.agr[((size_t)(k % P.AR) * P.NK + e.z) * P.C + cl];
+      unsigned long long* a = &P.agr[((size_t)(k % P.AR) * SH_NK(P) + e.z) * P.C + cl];
       PXS_TALLY_AT(P, x.blk, TC_AGREE, a, false);
       const unsigned long long v = *a;
       const uint32_t tv = (uint32_t)(v >> 40);
@@ -1081,7 +1081,7 @@ __global__ void __launch_bounds__(max_threads<NT>(), min_waves<NT>()) sim_steps(
     const size_t i = rc(P, x.r, x.c);
     x.kc = P.kc[x.c];
     x.flags = P.flags[i];
-    x.kvver = P.kv ? P.kv_ver[i] : 0u;
+    x.kvver = SH_kv(P) ? P.kv_ver[i] : 0u;
     Proto::template load<NT>(P, x);
   }
 #pragma unroll
@@ -1157,7 +1157,7 @@ __global__ void __launch_bounds__(max_threads<NT>(), min_waves<NT>()) sim_steps(
     const uint32_t r = x.r;
     const uint64_t c = x.c;
     P.flags[rc(P, r, c)] = x.flags;
-    if (P.kv) P.kv_ver[rc(P, r, c)] = x.kvver;
+    if (SH_kv(P)) P.kv_ver[rc(P, r, c)] = x.kvver;
     Proto::template store<NT>(P, x);
 #pragma unroll
     for (uint32_t k = 1; k < PAXISIM_NMSG; k++)
@@ -1333,7 +1333,7 @@ __device__ __forceinline__ void step_async(const Params& P, Rep<NT>& x, uint64_t
         if (s < NS) x.l_cnt[((box0 + s) << 6) | x.lane] = 0;
       if (x.stop) atomicMin(&x.l_poison[x.lane], x.t);
       P.flags[ri0] = x.flags;
-      if (P.kv) P.kv_ver[ri0] = x.kvver;
+      if (SH_kv(P)) P.kv_ver[ri0] = x.kvver;
       Proto::template store<NT>(P, x);
       if constexpr (Proto::step_scratch) Proto::template step_end<NT>(P, x);
       rep_counters_flush<NT>(P, x);
@@ -1349,7 +1349,7 @@ __device__ __forceinline__ void step_async(const Params& P, Rep<NT>& x, uint64_t
       x.l_c = reinterpret_cast<uint32_t*>(img + P.img.off_c);
       ri0 = rc(P, r, x.c);
       x.flags = P.flags[ri0];
-      x.kvver = P.kv ? P.kv_ver[ri0] : 0u;
+      x.kvver = SH_kv(P) ? P.kv_ver[ri0] : 0u;
       Proto::template load<NT>(P, x);
       if constexpr (Proto::step_scratch) Proto::template step_begin<NT>(P, x, scr);
       rep_counters_zero<NT>(x);
@@ -1359,8 +1359,8 @@ __device__ __forceinline__ void step_async(const Params& P, Rep<NT>& x, uint64_t
       x.im = 0;
       x.rw = 0;
       x.hs = step_key(x.kc, x.t);
-      if (P.late_workers) client_start<NT>(P, x);
-      const ScriptedStep sc = P.nfaults ? scripted_scan<NT>(P, x) : ScriptedStep{0u, 0u, 0ull, false};
+      if (SH_late_workers(P)) client_start<NT>(P, x);
+      const ScriptedStep sc = SH_nfaults(P) ? scripted_scan<NT>(P, x) : ScriptedStep{0u, 0u, 0ull, false};
       x.crashed = sc.crash;
       box0 = (x.b0 * N + r) * NS;
       if (PXS_LAT) {   // the inbox as this step finds it (trace_kernel.h)
@@ -1492,7 +1492,7 @@ __device__ __forceinline__ bool inbox_any(const Rep<NT>& x, uint32_t r, uint32_t
 }
 template <int NT>
 __device__ __forceinline__ bool late_start(const Params& P, uint32_t t, uint32_t r) {
-  for (uint32_t m = P.late_workers; m; m &= m - 1u) {
+  for (uint32_t m = SH_late_workers(P); m; m &= m - 1u) {
     const uint32_t w = (uint32_t)__builtin_ctz(m);
     if (P.start_step[w] == t && P.target[w] == r) return true;
   }
@@ -1578,9 +1578,9 @@ __device__ __forceinline__ void serial_tile(const Params& P, uint32_t blk, uint3
         const size_t i = rc(P, r, x.c);
         PXS_TALLY_AT(P, x.blk, TC_ROW_LD, &P.flags[i], false);
         x.flags = P.flags[i];
-        x.kvver = P.kv ? P.kv_ver[i] : 0u;
+        x.kvver = SH_kv(P) ? P.kv_ver[i] : 0u;
 #ifdef PXS_TALLY
-        if (P.kv) PXS_TALLY_AT(P, x.blk, TC_ROW_LD, &P.kv_ver[i], false);
+        if (SH_kv(P)) PXS_TALLY_AT(P, x.blk, TC_ROW_LD, &P.kv_ver[i], false);
 #endif
         const uint32_t flags0 = row_dirty_on<Proto>() ? x.flags : 0u, kvver0 = row_dirty_on<Proto>() ? x.kvver : 0u;
         Proto::template load<NT>(P, x);
@@ -1607,7 +1607,7 @@ __device__ __forceinline__ void serial_tile(const Params& P, uint32_t blk, uint3
           PXS_TALLY_AT(P, x.blk, TC_ROW_ST, &P.flags[i], true);
           P.flags[i] = x.flags;
         }
-        if (P.kv && (!row_dirty_on<Proto>() || x.kvver != kvver0)) {
+        if (SH_kv(P) && (!row_dirty_on<Proto>() || x.kvver != kvver0)) {
           PXS_TALLY_AT(P, x.blk, TC_ROW_ST, &P.kv_ver[i], true);
           P.kv_ver[i] = x.kvver;
         }

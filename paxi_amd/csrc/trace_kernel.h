@@ -36,7 +36,7 @@ namespace pxs {
 constexpr uint32_t TR_NONE = 0xFFFFFFFFu;   // tr_row: the cluster is not traced
 
 __host__ __device__ inline size_t trace_row(const Params& P, uint32_t row, uint32_t r) {
-  return (size_t)row * P.N + r;
+  return (size_t)row * SH_N(P) + r;
 }
 
 // Replica r of local cluster cl begins step t with the inbox boxes box0 + s, s < NS.

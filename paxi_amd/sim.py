@@ -128,6 +128,10 @@ def load_library():
             fn = getattr(L, name)
             fn.restype = C.c_int
             fn.argtypes = args
+    # which step-kernel unit a handle runs (include/paxisim_shape.h): likewise
+    if hasattr(L, "paxisim_step_unit"):
+        L.paxisim_step_unit.restype = C.c_int
+        L.paxisim_step_unit.argtypes = [C.c_void_p, P(C.c_uint32)]
     if L.paxisim_abi_version() != abi.ABI_VERSION:
         raise PaxisimError("ABI version mismatch between paxi_amd/abi.py and libpaxisim.so")
     _lib = L
@@ -153,7 +157,7 @@ EXPORTED = ["paxisim_abi_version", "paxisim_build_id", "paxisim_last_error", "pa
             "paxisim_trace_enable", "paxisim_trace_read", "paxisim_trace_totals",
             "paxisim_snapshot_size", "paxisim_snapshot", "paxisim_restore", "paxisim_fork", "paxisim_snapshot_info",
             "paxisim_verdict_available", "paxisim_verdicts", "paxisim_find", "paxisim_verdict_counts",
-            "paxisim_select_words"]
+            "paxisim_select_words", "paxisim_step_unit"]
 
 
 def consensus_of_histories(histories):
@@ -240,6 +244,16 @@ class Simulation:
 
     def step(self, n):
         _check(load_library().paxisim_step(self.h, n))
+
+    def step_unit(self):
+        """paxisim_step_unit: the step-kernel unit the next launch runs - abi.UNIT_GENERIC, or
+        abi.UNIT_FIXED_PAXOS5 for a handle of the headline's fixed shape (include/paxisim_shape.h)."""
+        fn = getattr(load_library(), "paxisim_step_unit", None)
+        if fn is None:
+            raise PaxisimError(f"{LIB_PATH} was built without paxisim_step_unit")
+        u = C.c_uint32()
+        _check(fn(self.h, C.byref(u)))
+        return u.value
 
     def sync(self):
         _check(load_library().paxisim_sync(self.h))
