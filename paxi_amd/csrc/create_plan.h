@@ -37,7 +37,7 @@ struct Knobs {
   uint32_t groups = 4;            // PAXISIM_GROUPS: cluster groups per workgroup at most (tuning)
   uint32_t stage = 16;            // PAXISIM_STAGE: staged picks per replica at most (tuning)
   bool compact = true;            // PAXISIM_COMPACT=0 turns compaction off (A/B)
-  bool phase_sort = PXS_PHASE_SORT != 0;   // PAXISIM_PHASE_SORT
+  bool phase_sort = true;   // PAXISIM_PHASE_SORT (A/B r4h, config 2: 12.87-13.17 -> 16.05-16.33 G msgs/s)
   uint32_t phase_period = 3;      // PAXISIM_PHASE_PERIOD
   uint32_t pipe = 4;              // PAXISIM_PIPE: chunks per launch at most (1: off)
   bool has_pipe_spin = false;     // PAXISIM_PIPE_SPIN: the poll limit of a chunk wait (tests)
@@ -347,12 +347,8 @@ inline int plan_lds(Params& P, const Knobs& kn, const KernelFacts& f) {
   if (f.serial) {   // one tile per workgroup; LDS: the image tail and the arrival counts
     P.G = 1;
     P.J = 0;
-    P.lds_tail = PXS_CLIENT_LDS ? P.img.off_wcur : P.img.off_poison;
+    P.lds_tail = P.img.off_wcur;
     P.lds_bytes = base - P.lds_tail;
-    if (PXS_WP_SCRATCH && P.protocol == PAXISIM_WPAXOS && P.wlds) {   // the replica-step instance scratch (wpaxos_kernel.h)
-      P.off_wscr = base;
-      P.lds_bytes += P.keys * WP_WORDS * LANES * 4u;
-    }
     // phase binning (Paxos, with compaction): per-residue record counts after the rest
     if (P.protocol == PAXISIM_PAXOS && kn.compact && kn.phase_sort) {
       P.phase_period = kn.phase_period;

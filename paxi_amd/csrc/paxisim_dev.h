@@ -163,8 +163,8 @@ struct Params {
   Image img;
   uint32_t J, off_stage;   // LDS stage: J staged picks per replica at LDS byte off_stage ([r][J][64] x 16 B)
   uint32_t lds_bytes;      // LDS per cluster group (16-B multiple): the image + the stage
-  uint32_t lds_tail;       // serial kernel: the image bytes [lds_tail, bytes) are staged in LDS (PXS_CLIENT_LDS)
-  uint32_t off_wscr;       // serial kernel, WPaxos (wlds): LDS byte offset of the replica-step instance scratch [K][5][lane]
+  uint32_t lds_tail;       // serial kernel: the image bytes [lds_tail, bytes) are staged in LDS (from the client tables on)
+  uint32_t off_wscr;       // 0 (was the LDS offset of a WPaxos replica-step scratch; kept for the layout of Params and snapshots)
   uint32_t G;              // cluster groups (64-cluster tiles) per workgroup
   uint32_t rec_per_block;  // D*N*NS*M*64
   const DevFault* faults;
@@ -271,13 +271,9 @@ struct Params {
 constexpr uint32_t WP_WORDS = 5;
 // Instance index of (blk, key k, replica r, lane) in the per-instance HBM
 // arrays (wst, wdig, wlog, wpend, wpx).  Key-major keeps one key's 64 lanes
-// together; lane-major (PXS_WP_LANEMAJOR) keeps one lane's K instances
-// together, so the instances a replica-step binds share few lines.
-#ifndef PXS_WP_LANEMAJOR
-#define PXS_WP_LANEMAJOR 0
-#endif
+// together (lane-major, one lane's K instances together, was measured in round 4:
+// profiles/r4/config5_layout.json).
 __device__ __forceinline__ size_t wp_si(const Params& P, uint64_t blk, uint32_t k, uint32_t r, uint32_t lane) {
-  if (PXS_WP_LANEMAJOR) return ((blk * SH_N(P) + r) * 64u + lane) * P.keys + k;
   return ((blk * P.keys + k) * SH_N(P) + r) * 64u + lane;
 }
 __device__ __forceinline__ uint32_t* wp_img(const Params& P, uint64_t blk, uint32_t k, uint32_t r, uint32_t lane) {
@@ -464,24 +460,10 @@ __device__ __forceinline__ void stamp_case(const Params& P, uint32_t blk, uint32
 #define PXS_SUB_T1(v, k)
 #endif
 
-// The serial kernel keeps the client tables (wcur / wiss) in the HBM image
-// (0) or stages them into LDS with the mailbox counts (1, A/B).
-#ifndef PXS_CLIENT_LDS
-#define PXS_CLIENT_LDS 1   // (A/B r3: the HBM tables cost config 2 6%, configs 4 and 5 4%)
-#endif
-
-// The serial kernel's WPaxos replica-step scratch (wpaxos_kernel.h step_begin):
-// the current replica's instance scalars in LDS.  Off: the scratch costs more
-// in tiles per CU (8 -> 5 on config 5) than it saves (A/B r3: -35%).
-#ifndef PXS_WP_SCRATCH
-#define PXS_WP_SCRATCH 0
-#endif
-
-// Phase binning of live clusters at compaction; the default,
-// overridden at run time by PAXISIM_PHASE_SORT=0/1
-#ifndef PXS_PHASE_SORT
-#define PXS_PHASE_SORT 1   // (A/B r4h, config 2: 12.87-13.17 -> 16.05-16.33 G msgs/s)
-#endif
+// The serial kernel stages the client tables (wcur / wiss) into LDS with the
+// mailbox counts (A/B r3: in the HBM image they cost config 2 6%, configs 4 and 5 4%).
+// It has no LDS scratch for a WPaxos replica's instance scalars: that cost more
+// in tiles per CU (8 -> 5 on config 5) than it saved (A/B r3: -35%).
 
 // ---- SoA addressing --------------------------------------------------------
 __device__ __forceinline__ size_t rc(const Params& P, uint32_t r, uint64_t c) { return (size_t)r * P.C + c; }

@@ -395,9 +395,6 @@ __device__ __forceinline__ void ghost_p2b(const Params& P, Rep<NT>& x, int32_t m
   }
 }
 
-#ifndef PXS_P2B_EAGER
-#define PXS_P2B_EAGER 0   // 1: HandleP2b reads the entry's ack word with its ballot and flags (A/B)
-#endif
 template <int NT>
 __device__ __forceinline__ bool in_window(const Params& P, const Rep<NT>& x, int32_t s) {
   return s >= x.execute && s < x.execute + (int32_t)SH_W(P);
@@ -471,16 +468,7 @@ __device__ __forceinline__ void handle_request(const Params& P, Rep<NT>& x, uint
 // is what the key holds at this point of the executed log.
 // Database.Execute's return value (db.go:103-114): the key's value before cmd.
 // A plain load: only the reply's store consumes it, so the wait for it lands
-// there rather than here (PXS_KV_LDG=1: wait at once, A/B).
-#ifndef PXS_KV_LDG
-#define PXS_KV_LDG 0
-#endif
-#ifndef PXS_AGREE_POST
-#define PXS_AGREE_POST 1    // 0: no agreement-ring arrivals (A/B attribution only)
-#endif
-#ifndef PXS_REPLY_VALUE
-#define PXS_REPLY_VALUE 1   // 0: replies carry no value (A/B attribution only; not the reference's behaviour)
-#endif
+// there rather than here.
 // (the key is computed once per executed command: kv_key)
 template <int NT>
 __device__ __forceinline__ uint32_t kv_key(const Params& P, Rep<NT>& x, uint32_t h, uint32_t cmd) {
@@ -489,10 +477,9 @@ __device__ __forceinline__ uint32_t kv_key(const Params& P, Rep<NT>& x, uint32_t
 }
 template <int NT>
 __device__ __forceinline__ uint32_t kv_get(const Params& P, Rep<NT>& x, uint32_t key) {
-  if (!PXS_REPLY_VALUE) return 0u;
   const uint32_t* a = &P.kv_val[((size_t)key * nrep<NT>(P) + x.r) * P.C + x.c];
   PXS_TALLY_AT(P, x.blk, TC_KV_LD, a, false);
-  return PXS_KV_LDG ? ldg(a) : *a;
+  return *a;
 }
 template <int NT>
 __device__ __forceinline__ void kv_exec(const Params& P, Rep<NT>& x, uint32_t h, uint32_t key, uint32_t cmd) {
@@ -555,7 +542,7 @@ __device__ __forceinline__ void paxos_exec(const Params& P, Rep<NT>& x, uint32_t
       PXS_TALLY_AT(P, x.blk, TC_CKPT, &P.ck_d[ci], true);
       P.ck_e[ci] = (uint32_t)x.execute;
       P.ck_d[ci] = x.digest;
-      if (P.AR && PXS_AGREE_POST) agree_post<NT>(P, x, (uint32_t)x.execute / CKI);
+      if (P.AR) agree_post<NT>(P, x, (uint32_t)x.execute / CKI);
     }
   }
 }
@@ -693,7 +680,6 @@ __device__ __forceinline__ void paxos_handle_p2b(const Params& P, Rep<NT>& x, ui
   const uint32_t i = eidx<NT>(P, x, ms);
   const uint32_t c = eb(x, i);
   const uint32_t eb0 = ea(x, i);
-  const uint32_t ea0 = PXS_P2B_EAGER ? ec(x, i) : 0u;   // (HBM window: the three words in one round trip)
   if (!(c & EF_EXISTS) || mb < eb0 || (c & EF_COMMIT)) return;
   PXS_SUB_T1(pxs_e0, 10)
   if (mb > x.ballot) {
@@ -707,7 +693,7 @@ __device__ __forceinline__ void paxos_handle_p2b(const Params& P, Rep<NT>& x, ui
       return;
     }
     PXS_SUB_T0(pxs_a0)
-    const uint32_t ack = (PXS_P2B_EAGER ? ea0 : ec(x, i)) | (1u << src);
+    const uint32_t ack = ec(x, i) | (1u << src);
     set_c(x, i, ack);
     PXS_SUB_T1(pxs_a0, 11)
     if (quorum_ok(P, SH_q2(P), ack)) {
@@ -788,11 +774,10 @@ __device__ __forceinline__ bool p2b_absorb(const Params& P, Rep<NT>& x, uint32_t
   const uint32_t i = eidx<NT>(P, x, ms);
   const uint32_t c = eb(x, i);
   const uint32_t eb0 = ea(x, i);
-  const uint32_t ea0 = PXS_P2B_EAGER ? ec(x, i) : 0u;
   if (!(c & EF_EXISTS) || mb < eb0 || (c & EF_COMMIT)) return true;
   if (bal_id(mb) == x.r && mb == eb0) {
     if (!(c & EF_QUORUM)) return false;                 // nil quorum: the full handler poisons
-    const uint32_t ack = (PXS_P2B_EAGER ? ea0 : ec(x, i)) | (1u << src);
+    const uint32_t ack = ec(x, i) | (1u << src);
     if (quorum_ok(P, SH_q2(P), ack)) return false;          // commit: the full handler
     set_c(x, i, ack);
   }
@@ -808,7 +793,6 @@ __device__ __forceinline__ bool p2b_absorb(const Params& P, Rep<NT>& x, uint32_t
 // ---------------------------------------------------------------------------
 struct PaxosProto {
   static constexpr uint32_t kind = PAXISIM_PAXOS;
-  static constexpr bool step_scratch = false;   // (no per-replica-step LDS scratch: sim_core.h sim_serial)
   template <int NT>
   __device__ static __forceinline__ void load(const Params& P, Rep<NT>& x) {
     const size_t i = rc(P, x.r, x.c);

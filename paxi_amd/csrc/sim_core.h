@@ -100,62 +100,37 @@ __device__ __forceinline__ uint32_t lsel(const uint32_t (&a)[Rep<NT>::NL], uint3
 // socket.Send (socket.go:66-109): crash -> drop -> flaky -> slow, then the
 // bounded (link, arrival-step) bucket.  Returns the record index to write.
 // ---------------------------------------------------------------------------
-// One exit (PXS_SEND_ONE_EXIT, on): the filter's verdict is a value and the
-// drop is counted once at the end.  The early-return form - a return inside
-// the divergent Flaky branch - is the shape LLVM has miscompiled in three
-// builds (a register live across the branch held the Flaky
-// probability, or another stale value, on the dropping lanes' path to the
-// join); with one exit neither reproducer of round 5 diverges
-// (gpurun_out/r5l).  0 keeps the early returns (A/B, reproducers).
-#ifndef PXS_SEND_ONE_EXIT
-#define PXS_SEND_ONE_EXIT 1
-#endif
+// One exit: the filter's verdict is a value and the drop is counted once at
+// the end.  The early-return form - a return inside the divergent Flaky
+// branch - is the shape LLVM has miscompiled in three builds (DESIGN.md §5.3:
+// a register live across the branch held the Flaky probability, or another
+// stale value, on the dropping lanes' path to the join); with one exit neither
+// reproducer of round 5 diverges (r5l).  The early returns survive
+// only in the pinned reproducer's sources (paxi_amd/guard/pinned).
 template <int NT>
 __device__ __forceinline__ bool send_begin(const Params& P, Rep<NT>& x, uint32_t to, uint32_t nrec, uint32_t& ri) {
   const uint32_t seq = x.send_seq++;
   x.sent++;
-  if constexpr (PXS_SEND_ONE_EXIT) {
-    // crash, unknown id (socket.go:86-88) and drop were folded into dmask at step start
-    bool ok = to < nrep<NT>(P) && !((x.dmask >> to) & 1u);
-    if (ok && ((x.fmask >> to) & 1u)) {                // flaky (socket.go:77-81), scripted only
-      uint32_t p = 0;
-      scripted(P, PAXISIM_FAULT_FLAKY, x.gid, x.r, to, x.t, &p);
-      ok = !ppm_hit(draw(x.hs, tag(PUR_FLAKY, x.r, seq)), p);
-    }
-    // slow (socket.go:99-106); `to & 15` keeps the shift defined for an unknown id,
-    // whose bucket is never written
-    uint32_t b = x.b0 + 1u + (uint32_t)((x.dly >> (4u * (to & 15u))) & 15u);
-    if (b >= P.D) b -= P.D;
-    const uint32_t box = (b * nrep<NT>(P) + (ok ? to : 0u)) * SH_NS(P) + x.r;
-    const uint32_t k = ok ? (uint32_t)x.l_cnt[(box << 6) | x.lane] : 0u;
-    const bool ovf = ok && k + nrec > P.M;
-    if (ovf) x.flags |= PAXISIM_F_MBOX_OVF | PAXISIM_F_UNFAITHFUL;
-    ok = ok && !ovf;
-    x.dropped += ok ? 0u : 1u;
-    if (ok) x.l_cnt[(box << 6) | x.lane] = (uint8_t)(k + nrec);
-    ri = ((box * P.M + k) << 6) | x.lane;
-    return ok;
-  }
   // crash, unknown id (socket.go:86-88) and drop were folded into dmask at step start
-  if (to >= nrep<NT>(P) || ((x.dmask >> to) & 1u)) { x.dropped++; return false; }
-  if ((x.fmask >> to) & 1u) {                          // flaky (socket.go:77-81), scripted only
+  bool ok = to < nrep<NT>(P) && !((x.dmask >> to) & 1u);
+  if (ok && ((x.fmask >> to) & 1u)) {                // flaky (socket.go:77-81), scripted only
     uint32_t p = 0;
     scripted(P, PAXISIM_FAULT_FLAKY, x.gid, x.r, to, x.t, &p);
-    if (ppm_hit(draw(x.hs, tag(PUR_FLAKY, x.r, seq)), p)) { x.dropped++; return false; }
+    ok = !ppm_hit(draw(x.hs, tag(PUR_FLAKY, x.r, seq)), p);
   }
-  uint32_t b = x.b0 + 1u + (uint32_t)((x.dly >> (4u * to)) & 15u);   // slow (socket.go:99-106)
+  // slow (socket.go:99-106); `to & 15` keeps the shift defined for an unknown id,
+  // whose bucket is never written
+  uint32_t b = x.b0 + 1u + (uint32_t)((x.dly >> (4u * (to & 15u))) & 15u);
   if (b >= P.D) b -= P.D;
-  const uint32_t box = (b * nrep<NT>(P) + to) * SH_NS(P) + x.r;
-  uint8_t* cp = &x.l_cnt[(box << 6) | x.lane];
-  const uint32_t k = *cp;
-  if (k + nrec > P.M) {
-    x.flags |= PAXISIM_F_MBOX_OVF | PAXISIM_F_UNFAITHFUL;
-    x.dropped++;
-    return false;
-  }
-  *cp = (uint8_t)(k + nrec);
+  const uint32_t box = (b * nrep<NT>(P) + (ok ? to : 0u)) * SH_NS(P) + x.r;
+  const uint32_t k = ok ? (uint32_t)x.l_cnt[(box << 6) | x.lane] : 0u;
+  const bool ovf = ok && k + nrec > P.M;
+  if (ovf) x.flags |= PAXISIM_F_MBOX_OVF | PAXISIM_F_UNFAITHFUL;
+  ok = ok && !ovf;
+  x.dropped += ok ? 0u : 1u;
+  if (ok) x.l_cnt[(box << 6) | x.lane] = (uint8_t)(k + nrec);
   ri = ((box * P.M + k) << 6) | x.lane;
-  return true;
+  return ok;
 }
 
 // The scripted faults of this replica at this step (socket.go:163-199 Drop /
@@ -250,41 +225,11 @@ __device__ __forceinline__ void broadcast1(const Params& P, Rep<NT>& x, uint32_t
 // and emission walks destinations in index order, so every link sees its
 // records in exactly the order the handlers issued them.
 // ---------------------------------------------------------------------------
-#ifndef PXS_FLUSH1_9
-#define PXS_FLUSH1_9 0   // 1: 9-replica WPaxos kernel flushes in one pass (A/B r2: +4% at 153 spilled VGPRs, -3% at 101)
-#endif
+// (A one-pass flush for the 9-replica WPaxos kernel: A/B r2 +4% at 153 spilled VGPRs, -3% at 101; retired.)
 template <int NT>
 __device__ __forceinline__ void intent_flush(const Params& P, Rep<NT>& x) {
   if (!x.im) return;
   constexpr uint32_t NU = NT ? (uint32_t)NT : (uint32_t)PAXISIM_MAX_N;
-  if (NT == 9 && PXS_FLUSH1_9 && x.pk) {   // (the per-key kernel: A/B r2 +, the Multi-Paxos LDS-window one -)
-#pragma unroll
-    for (uint32_t d = 0; d < NU; d++) {
-      if (!((x.im >> d) & 1u)) continue;
-      const uint32_t seq = x.send_seq++;
-      x.sent++;
-      if ((x.dmask >> d) & 1u) { x.dropped++; continue; }
-      if ((x.fmask >> d) & 1u) {
-        uint32_t p = 0;
-        scripted(P, PAXISIM_FAULT_FLAKY, x.gid, x.r, d, x.t, &p);
-        if (ppm_hit(draw(x.hs, tag(PUR_FLAKY, x.r, seq)), p)) { x.dropped++; continue; }
-      }
-      uint32_t b = x.b0 + 1u + (uint32_t)((x.dly >> (4u * d)) & 15u);
-      if (b >= P.D) b -= P.D;
-      const uint32_t box = (b * NU + d) * SH_NS(P) + x.r;
-      const uint32_t k = x.l_cnt[(box << 6) | x.lane];
-      if (k + 1u > P.M) {
-        x.flags |= PAXISIM_F_MBOX_OVF | PAXISIM_F_UNFAITHFUL;
-        x.dropped++;
-        continue;
-      }
-      x.l_cnt[(box << 6) | x.lane] = (uint8_t)(k + 1u);
-      PXS_TALLY_AT(P, x.blk, TC_REC_ST, &x.rec[((box * P.M + k) << 6) | x.lane], true);
-      x.rec[((box * P.M + k) << 6) | x.lane] = make_uint4(x.iw0, x.iw1, x.iw2, x.iw3);
-    }
-    x.im = 0;
-    return;
-  }
   // pass 1: the bucket count of every destination (independent LDS reads:
   // each destination has its own box, so reading them up front is exact)
   uint32_t box[NU], k[NU];
@@ -426,13 +371,8 @@ __device__ __forceinline__ bool wl_write(const Params& P, uint32_t kc, uint32_t 
   return wl_write_h(P, wl_hash(kc, cid));
 }
 
-#ifndef PXS_REPLY_STORE
-#define PXS_REPLY_STORE 1   // 0: the worker's last Reply.Value is not kept (A/B attribution only)
-#endif
-#ifndef PXS_REPLY_DEFER
-#define PXS_REPLY_DEFER 1   // the Reply.Value store waits until the end of the merge trip
-#endif
-// The value usually comes from a load issued just before the reply (Execute's
+// The worker's last Reply.Value is stored at the end of the merge trip.  The
+// value usually comes from a load issued just before the reply (Execute's
 // previous value, paxos_kernel.h kv_get): storing it at the end of the trip
 // lets the handler go on without waiting for that load.
 template <int NT>
@@ -457,13 +397,9 @@ __device__ __forceinline__ void client_reply(const Params& P, Rep<NT>& x, uint32
   if (PXS_LAT) {
     if (P.ch_cap) chist_record(P, w, x.gid - P.cluster_base, x.c, cid, value, x.t);   // the op (chist_kernel.h)
   }
-  if (PXS_REPLY_STORE && PXS_REPLY_DEFER) {
-    reply_flush<NT>(P, x);
-    x.rw = w + 1u;
-    x.rv = value;
-  } else if (PXS_REPLY_STORE) {
-    P.wrep[(size_t)w * P.C + x.c] = value;
-  }
+  reply_flush<NT>(P, x);
+  x.rw = w + 1u;
+  x.rv = value;
   const uint32_t issued = x.l_wiss[wi];
   if (SH_max_requests(P) == 0 || issued < SH_max_requests(P)) {
     const uint64_t nc = 1ull + w + (uint64_t)P.WK * issued;
@@ -545,28 +481,9 @@ __device__ __forceinline__ void fault_process(const Params& P, Rep<NT>& x, uint3
   }
 }
 
-// Same-trip absorption of send-free P2bs (below) in the 9-replica Paxos
-// kernel too; 0 builds it without (A/B of register pressure vs trips).
-#ifndef PXS_ABSORB9
-#define PXS_ABSORB9 1
-#endif
+// Same-trip absorption of send-free P2bs (replica_step): messages absorbed per trip.
 #ifndef PXS_ABSORB_MAX
-#define PXS_ABSORB_MAX 2   // messages absorbed per trip (A/B: 2 > 3 > 4 > 6 on config 2)
-#endif
-#ifndef PXS_ABSORB_ABD
-#define PXS_ABSORB_ABD 0
-#endif
-#ifndef PXS_AGR_SLOT
-#define PXS_AGR_SLOT 0    // 1: the Multi-Paxos ring indexed by slot too (round 4; diagnostic A/B only - wrong under compaction)
-#endif
-#ifndef PXS_WP_ABSORB
-#define PXS_WP_ABSORB 0   // WPaxos same-key P2b absorption (wpaxos_kernel.h): 0 off, 1 the r4l experiment, 2 fixed
-#endif
-#ifndef PXS_FLUSH_LATE
-#define PXS_FLUSH_LATE 1
-#endif
-#ifndef PXS_LINK_LATE
-#define PXS_LINK_LATE 1   // the unstaged loop issues its first record load before the link state's (replica_step)
+#define PXS_ABSORB_MAX 2   // (A/B: absorbing more than 2 per trip was slower, 2 > 3 > 4 > 6 on config 2)
 #endif
 #ifndef PXS_PREFETCH2
 #define PXS_PREFETCH2 0   // 1: unstaged loop loads records two messages ahead (A/B r2l: -13% on config 2, more spills)
@@ -578,9 +495,6 @@ __device__ __forceinline__ void fault_process(const Params& P, Rep<NT>& x, uint3
 // Records left per source in the merge.  9-replica kernels pack them into
 // bytes (four sources a register: counts are at most M <= 255), which frees
 // seven registers across the merge loop; the others keep one a source.
-#ifndef PXS_PACKREM9
-#define PXS_PACKREM9 1
-#endif
 template <uint32_t NS, bool PACK>
 struct RemT {
   uint32_t v[NS];
@@ -639,7 +553,7 @@ __device__ __forceinline__ void replica_step(const Params& P, Rep<NT>& x
   // The random fault process and the step's link masks.  Nothing before the
   // first handler's sends reads them, so the unstaged loop runs this after it
   // has issued its first record load: the link state's HBM round trip then
-  // overlaps the record's instead of preceding it (PXS_LINK_LATE).
+  // overlaps the record's instead of preceding it.
   auto link_step = [&]() {
     // link state exists only under a random fault process (without one it stays 0)
     const bool random_faults = P.drop_ppm || P.slow_ppm;
@@ -658,7 +572,7 @@ __device__ __forceinline__ void replica_step(const Params& P, Rep<NT>& x
     fault_process<NT>(P, x, du, su);
     link_masks<NT>(P, x, du, su, sc);
   };
-  constexpr bool LINK_LATE = !STAGED && PXS_LINK_LATE;
+  constexpr bool LINK_LATE = !STAGED;
   if constexpr (!LINK_LATE) link_step();
 
   const uint32_t box0 = (x.b0 * N + x.r) * NS;          // inbox boxes: box0 + src
@@ -668,7 +582,7 @@ __device__ __forceinline__ void replica_step(const Params& P, Rep<NT>& x
   // per source: records left (rem) and the step's initial count, packed in
   // bytes (c0w), so a source's FIFO position is c0 - rem without a register each
   constexpr uint32_t NCW = (NSMAX + 3u) / 4u;
-  RemT<NSMAX, NT == 9 && PXS_PACKREM9> rem;
+  RemT<NSMAX, NT == 9> rem;
   uint32_t c0w[NCW], total = 0;
   rem.clear();
 #pragma unroll
@@ -852,13 +766,8 @@ __device__ __forceinline__ void replica_step(const Params& P, Rep<NT>& x
     const unsigned long long q2t = stamp();
     st.disp += q2t - q1;
 #endif
-#if !PXS_FLUSH_LATE
-    intent_flush<NT>(P, x);                             // one emit point for all lanes
-#endif
     PXS_SUB_T0(pxs_ab0)
-    if constexpr ((Proto::kind == PAXISIM_PAXOS && (PXS_ABSORB9 || NT != 9)) ||
-                  (Proto::kind == PAXISIM_ABD && PXS_ABSORB_ABD) ||
-                  (Proto::kind == PAXISIM_WPAXOS && PXS_WP_ABSORB)) {
+    if constexpr (Proto::kind == PAXISIM_PAXOS) {
       // Next messages whose handling is short and send-free (a P2b that does
       // not complete a quorum: paxos.go:270-297) are handled in this same
       // trip, up to PXS_ABSORB_MAX of them.  Order, counters and state are exactly as
@@ -892,7 +801,6 @@ __device__ __forceinline__ void replica_step(const Params& P, Rep<NT>& x
       }
     }
     if constexpr (Proto::kind == PAXISIM_PAXOS) { PXS_SUB_T1(pxs_ab0, 12) }
-#if PXS_FLUSH_LATE
     // The handler's pending send is emitted after the absorbed messages (they
     // send nothing, so every link still sees its records in handler order):
     // the record loads issued while absorbing then precede this flush's
@@ -902,7 +810,6 @@ __device__ __forceinline__ void replica_step(const Params& P, Rep<NT>& x
     reply_flush<NT>(P, x);
     intent_flush<NT>(P, x);
     if constexpr (Proto::kind == PAXISIM_PAXOS) { PXS_SUB_T1(pxs_fl0, 13) }
-#endif
 #ifdef PXS_STAMPS
     fe = stamp();
     st.flush += fe - q2t;
@@ -980,7 +887,7 @@ __device__ __forceinline__ void agree_drain(const Params& P, const Rep<NT>& x, u
       // indexed by the cluster, not its slot: compaction does not move the ring
       // (paxisim.hip swap_slots).  Only Multi-Paxos compacts; elsewhere slot ==
       // cluster and the slot index is used as before
-      const uint64_t cl = Proto::kind == PAXISIM_PAXOS && !PXS_AGR_SLOT ? x.gid - P.cluster_base : x.c;
+      const uint64_t cl = Proto::kind == PAXISIM_PAXOS ? x.gid - P.cluster_base : x.c;
       unsigned long long* a = &P.agr[((size_t)(k % P.AR) * SH_NK(P) + e.z) * P.C + cl];
       PXS_TALLY_AT(P, x.blk, TC_AGREE, a, false);
       const unsigned long long v = *a;
@@ -1017,11 +924,10 @@ template <int NT> constexpr int min_waves() { return NT == 0 ? 4 : 3; }
 // workgroup runs alone on its CU and has LDS to spare (9 replicas, ABD's 3/5);
 // elsewhere the second copy of the loop costs registers the packed cluster
 // groups need.  StepOps::staged exports it (step_ops.h); paxisim.hip sets J = 0 without it.
-#ifndef PXS_STAGE5
-#define PXS_STAGE5 0   // 1: the 5-replica Paxos instance carries the staged loop too (A/B)
-#endif
+// (The 5-replica Paxos instance with the staged loop, one tile per CU: slower than the unstaged
+// kernel at the same occupancy, 5.39 against 6.96 G msgs/s.)
 template <int NT, class Proto> constexpr bool stage_built() {
-  return Proto::kind == PAXISIM_ABD ? NT != 0 : (NT == 9 || (PXS_STAGE5 && NT == 5 && Proto::kind == PAXISIM_PAXOS));
+  return Proto::kind == PAXISIM_ABD ? NT != 0 : NT == 9;
 }
 
 // The largest workgroup: as many N-wave cluster groups as min_waves slots per
@@ -1195,11 +1101,9 @@ __global__ void __launch_bounds__(max_threads<NT>(), min_waves<NT>()) sim_steps(
 #ifndef PXS_BUSY_FIRST
 #define PXS_BUSY_FIRST 1
 #endif
-#ifndef PXS_BUSY_FIRST_ALL
-#define PXS_BUSY_FIRST_ALL 0   // 1: every protocol (A/B r4i: Paxos -2% on config 2, -4% on config 4); default: WPaxos and ABD
-#endif
+// WPaxos and ABD only (A/B r4i, every protocol: Paxos -2% on config 2, -4% on config 4).
 template <int NT, class Proto> constexpr bool busy_first() {
-  return PXS_BUSY_FIRST && (PXS_BUSY_FIRST_ALL || Proto::kind == PAXISIM_WPAXOS || Proto::kind == PAXISIM_ABD);
+  return PXS_BUSY_FIRST && (Proto::kind == PAXISIM_WPAXOS || Proto::kind == PAXISIM_ABD);
 }
 template <int NT>
 __device__ __forceinline__ uint64_t replica_order(const Params& P, const Rep<NT>& x, uint32_t b0) {
@@ -1226,12 +1130,6 @@ __device__ __forceinline__ uint64_t replica_order(const Params& P, const Rep<NT>
   return order;
 }
 
-#ifndef PXS_PHASE_RECENT
-#define PXS_PHASE_RECENT 0   // 1: the residue counts cover the launch's second half only (fresher phase)
-#endif
-#ifndef PXS_PHASE_HYST
-#define PXS_PHASE_HYST 0   // percent a new residue must lead the current one by (phase binning)
-#endif
 #ifndef PXS_SERIAL_WAVES
 #define PXS_SERIAL_WAVES 2   // waves per SIMD the register budget must allow (2: <= 256 VGPRs; A/B r3: 3 waves at 168 VGPRs spill 127 and run 10-24% slower)
 #endif
@@ -1241,17 +1139,13 @@ __device__ __forceinline__ void rep_counters_zero(Rep<NT>& x) {
   for (uint32_t k = 0; k < PAXISIM_NMSG / 2; k++) x.dvp[k] = 0;
   x.client = x.sent = x.dropped = x.discarded = x.commits = x.replies = 0;
 }
-// PXS_COUNTER_ATOMIC: the per-replica-step counts go out as fire-and-forget
-// atomic adds (no load to wait for) instead of read-modify-writes
-#ifndef PXS_COUNTER_ATOMIC
-#define PXS_COUNTER_ATOMIC 1   // (A/B r3, config 2: +4.9%)
-#endif
+// The per-replica-step counts go out as fire-and-forget atomic adds (no load
+// to wait for) instead of read-modify-writes (A/B r3, config 2: +4.9%)
 #ifdef PXS_TALLY
 #define stat_add(p, v) (PXS_TALLY_AT(P, x.blk, TC_CNT, (p), true), stat_add_((p), (v)))
 #endif
 __device__ __forceinline__ void stat_add_(uint32_t* p, uint32_t v) {
-  if (PXS_COUNTER_ATOMIC) __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else *p += v;
+  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 #ifndef PXS_TALLY
 #define stat_add stat_add_
@@ -1271,176 +1165,6 @@ __device__ __forceinline__ void rep_counters_flush(const Params& P, const Rep<NT
   if (x.replies) stat_add(&P.stats[krc(P, ST_REPLIES, r, c)], x.replies);
 }
 
-// ---------------------------------------------------------------------------
-// Lane-asynchronous replica progress (PXS_LANE_ASYNC).  The
-// serial kernel's replica-steps of one step are independent (sends land in
-// later steps' buckets), so a lane need not wait at each replica-step for the
-// wave's busiest lane: here every lane walks its own cluster's replicas
-// (busiest first) and starts the next one as soon as its inbox is drained.
-// A trip handles one message for every lane that has one; starting a
-// replica-step (its registers and inbox counts) and finishing one (write-back,
-// counters) run in divergent branches of the same loop, and starts are batched
-// - taken when PXS_ASYNC_BATCH lanes wait or no lane has a message left - so
-// the wave does not pay a start for every lane that finishes.  Semantics are
-// the replica-step's exactly (replica_step's unstaged path, no absorption).
-// ---------------------------------------------------------------------------
-#ifndef PXS_LANE_ASYNC
-#define PXS_LANE_ASYNC 0
-#endif
-#ifndef PXS_ASYNC_BATCH
-#define PXS_ASYNC_BATCH 16
-#endif
-template <int NT, class Proto>
-__device__ __forceinline__ void step_async(const Params& P, Rep<NT>& x, uint64_t order, bool run, uint8_t* img,
-                                           uint8_t* scr) {
-  constexpr uint32_t NSMAX = NT ? (uint32_t)NT + 1u : (uint32_t)PAXISIM_MAX_N + 1u;
-  constexpr uint32_t NCW = (NSMAX + 3u) / 4u;
-  const uint32_t N = nrep<NT>(P), NS = N + 1u;
-  uint32_t k = run ? 0u : N;            // replica-steps started
-  bool act = false;                     // a replica-step in progress
-  size_t ri0 = 0;                       // rc() of the current replica
-  uint32_t box0 = 0, total = 0, u = 0, i = 0, src = 0, ri = 0;
-  uint4 m = make_uint4(0u, 0u, 0u, 0u);
-  RemT<NSMAX, NT == 9 && PXS_PACKREM9> rem;
-  uint32_t c0w[NCW];
-  rem.clear();
-#pragma unroll
-  for (uint32_t q = 0; q < NCW; q++) c0w[q] = 0;
-  auto pick = [&](uint32_t idx, uint32_t& psrc, uint32_t& pri) {
-    if (!(idx & 1u)) u = draw(x.hs, tag(PUR_ORDER, x.r, idx >> 1));
-    uint32_t pk = (((idx & 1u) ? (u >> 16) : (u & 0xFFFFu)) * total) >> 16;
-    bool found = false;
-    psrc = 0;
-    uint32_t p0 = 0;
-#pragma unroll
-    for (uint32_t s = 0; s < NSMAX; s++) {
-      const uint32_t rs = rem.get(s);
-      const bool here = !found && pk < rs;
-      if (here) { psrc = s; p0 = ((c0w[s >> 2] >> ((s & 3u) * 8u)) & 0xFFu) - rs; found = true; }
-      else if (!found) pk -= rs;
-    }
-    pri = (((box0 + psrc) * P.M + p0) << 6) | x.lane;
-  };
-  // Outer loop: finish the lanes whose replica-step is drained, start the next
-  // one of every lane that has one left; inner loop: merge trips as in
-  // replica_step, until no lane has a message or PXS_ASYNC_BATCH lanes wait.
-  for (;;) {
-    if (act && (total == 0u || x.stop)) {          // replica_step's tail and the serial kernel's write-back
-      act = false;
-      reply_flush<NT>(P, x);
-#pragma unroll
-      for (uint32_t s = 0; s < NSMAX; s++)
-        if (s < NS) x.l_cnt[((box0 + s) << 6) | x.lane] = 0;
-      if (x.stop) atomicMin(&x.l_poison[x.lane], x.t);
-      P.flags[ri0] = x.flags;
-      if (SH_kv(P)) P.kv_ver[ri0] = x.kvver;
-      Proto::template store<NT>(P, x);
-      if constexpr (Proto::step_scratch) Proto::template step_end<NT>(P, x);
-      rep_counters_flush<NT>(P, x);
-    }
-    if (!act && k < N) {                              // the lane's next replica, busiest first
-      const uint32_t r = (uint32_t)(order >> (4u * k)) & 15u;
-      k++;
-      act = true;
-      x.r = r;
-      x.ci = ~0u;
-      x.l_a = reinterpret_cast<uint32_t*>(img + P.img.off_a);
-      x.l_b = reinterpret_cast<uint32_t*>(img + P.img.off_b);
-      x.l_c = reinterpret_cast<uint32_t*>(img + P.img.off_c);
-      ri0 = rc(P, r, x.c);
-      x.flags = P.flags[ri0];
-      x.kvver = SH_kv(P) ? P.kv_ver[ri0] : 0u;
-      Proto::template load<NT>(P, x);
-      if constexpr (Proto::step_scratch) Proto::template step_begin<NT>(P, x, scr);
-      rep_counters_zero<NT>(x);
-      // replica_step's set-up (unstaged path)
-      x.send_seq = 0;
-      x.stop = false;
-      x.im = 0;
-      x.rw = 0;
-      x.hs = step_key(x.kc, x.t);
-      if (SH_late_workers(P)) client_start<NT>(P, x);
-      const ScriptedStep sc = SH_nfaults(P) ? scripted_scan<NT>(P, x) : ScriptedStep{0u, 0u, 0ull, false};
-      x.crashed = sc.crash;
-      box0 = (x.b0 * N + r) * NS;
-      if (PXS_LAT) {   // the inbox as this step finds it (trace_kernel.h)
-        if (P.tr_cap) trace_inbox(P, x.gid - P.cluster_base, x.r, x.t, x.lane, x.l_cnt, x.rec, box0, NS);
-      }
-      rem.clear();
-#pragma unroll
-      for (uint32_t q = 0; q < NCW; q++) c0w[q] = 0;
-      total = 0;
-#pragma unroll
-      for (uint32_t s = 0; s < NSMAX; s++) {
-        if (s < NS) {
-          uint32_t n = x.l_cnt[((box0 + s) << 6) | x.lane];
-          if (x.crashed && s < N && n) {                    // socket.Recv discards (socket.go:111-118)
-            for (uint32_t q = 0; q < n;) {
-              const uint32_t h = ldg(&x.rec[(((box0 + s) * P.M + q) << 6) | x.lane]).x;
-              x.discarded++;
-              q += rec_len(h);
-            }
-            n = 0;
-          }
-          rem.put(s, n);
-          c0w[s >> 2] |= n << ((s & 3u) * 8u);
-          total += n;
-        }
-      }
-      i = 0;
-      if (total) {
-        pick(0, src, ri);
-        m = x.rec[ri];
-      }
-      {   // the link state after the first record load (PXS_LINK_LATE)
-        const bool random_faults = P.drop_ppm || P.slow_ppm;
-        uint32_t du[Rep<NT>::NL], su[Rep<NT>::NL];
-#pragma unroll
-        for (uint32_t d = 0; d < Rep<NT>::NL; d++) {
-          du[d] = d < N && random_faults ? P.link_drop[krc(P, d, x.r, x.c)] : 0u;
-          su[d] = d < N && random_faults ? P.link_slow[krc(P, d, x.r, x.c)] : 0u;
-        }
-        fault_process<NT>(P, x, du, su);
-        link_masks<NT>(P, x, du, su, sc);
-      }
-    }
-    if (!__ballot(act)) break;
-    // merge trips; a lane whose inbox is drained waits here until the batch ends
-    for (;;) {
-      const bool busy = act && total != 0u && !x.stop;
-      const uint64_t bb = __ballot(busy);
-      if (!bb || __popcll(__ballot(!busy && (act || k < N))) >= PXS_ASYNC_BATCH) break;
-      if (busy) {
-        const uint32_t len = rec_len(m.x);
-        rem.sub(src, len);
-        total -= len;
-        uint32_t nsrc = 0, nri = 0;
-        uint4 nm = make_uint4(0u, 0u, 0u, 0u);
-        if (total) {
-          pick(i + 1u, nsrc, nri);
-          nm = x.rec[nri];
-        }
-        if (src == N) {
-          x.client++;
-          Proto::template client_request<NT>(P, x, m.w);
-        } else {
-          Proto::template dispatch<NT>(P, x, src, m, ri);
-        }
-        reply_flush<NT>(P, x);
-        intent_flush<NT>(P, x);
-        src = nsrc;
-        ri = nri;
-        m = nm;
-        i++;
-      }
-    }
-  }
-}
-template <int NT, class Proto> constexpr bool lane_async() {
-  // the busiest-first protocols without same-trip absorption (the merge loop above has none)
-  return PXS_LANE_ASYNC && Proto::kind == PAXISIM_WPAXOS && !PXS_WP_ABSORB;
-}
-
 #ifndef PXS_SERIAL_WAVES_ABD
 #define PXS_SERIAL_WAVES_ABD 3   // ABD's kernels fit 168 VGPRs without spilling
 #endif
@@ -1455,7 +1179,7 @@ template <class Proto> constexpr int serial_waves() {
 // work: a random fault process advancing its links, or a late worker whose
 // first request starts at this replica now (client_start).  Otherwise the
 // serial kernel skips such a lane's replica-step whole: no register rows
-// loaded or stored, no counters.  PXS_ROW_DIRTY: the per-replica rows (flags,
+// loaded or stored, no counters.  Dirty rows: the per-replica rows (flags,
 // database version) are written back only when they changed.  Both are on for
 // ABD only: mirrored A/Bs (gpurun_out/r6g2) give ABD (config 3) +4.4%, but
 // Multi-Paxos (config 2, where the random fault process leaves no replica-step
@@ -1465,23 +1189,14 @@ template <class Proto> constexpr int serial_waves() {
 // TU_FLAGS): config 4 has no random fault process and 41% of its wave-level
 // replica-steps are idle (phase-aligned followers), +6.3% (gpurun_out/r6o;
 // with the dirty rows too only +2.6%).
-#ifndef PXS_SKIP_IDLE
-#define PXS_SKIP_IDLE 1
-#endif
-#ifndef PXS_ROW_DIRTY
-#define PXS_ROW_DIRTY 1
-#endif
 #ifndef PXS_SKIP_IDLE_PAXOS
 #define PXS_SKIP_IDLE_PAXOS 0
 #endif
-#ifndef PXS_ROW_DIRTY_PAXOS
-#define PXS_ROW_DIRTY_PAXOS 0
-#endif
 template <class Proto> constexpr bool skip_idle_on() {
-  return PXS_SKIP_IDLE && (Proto::kind == PAXISIM_ABD || (PXS_SKIP_IDLE_PAXOS && Proto::kind == PAXISIM_PAXOS));
+  return Proto::kind == PAXISIM_ABD || (PXS_SKIP_IDLE_PAXOS && Proto::kind == PAXISIM_PAXOS);
 }
 template <class Proto> constexpr bool row_dirty_on() {
-  return PXS_ROW_DIRTY && (Proto::kind == PAXISIM_ABD || (PXS_ROW_DIRTY_PAXOS && Proto::kind == PAXISIM_PAXOS));
+  return Proto::kind == PAXISIM_ABD;
 }
 template <int NT>
 __device__ __forceinline__ bool inbox_any(const Rep<NT>& x, uint32_t r, uint32_t b0, uint32_t N) {
@@ -1521,13 +1236,8 @@ __device__ __forceinline__ void serial_tile(const Params& P, uint32_t blk, uint3
   x.blk = blk;
   x.c = (uint64_t)blk * LANES + x.lane;
   x.gid = P.cluster_base + P.cl_of[x.c];
-  if (PXS_CLIENT_LDS) {
-    x.l_wcur = reinterpret_cast<uint32_t*>(L + (P.img.off_wcur - tail));
-    x.l_wiss = reinterpret_cast<uint32_t*>(L + (P.img.off_wiss - tail));
-  } else {                                                   // client tables in the HBM image
-    x.l_wcur = reinterpret_cast<uint32_t*>(img + P.img.off_wcur);
-    x.l_wiss = reinterpret_cast<uint32_t*>(img + P.img.off_wiss);
-  }
+  x.l_wcur = reinterpret_cast<uint32_t*>(L + (P.img.off_wcur - tail));
+  x.l_wiss = reinterpret_cast<uint32_t*>(L + (P.img.off_wiss - tail));
   x.l_poison = reinterpret_cast<uint32_t*>(L + (P.img.off_poison - tail));
   x.l_cnt = L + (P.img.off_cnt - tail);
   x.l_agn = L + (P.off_agn - tail);
@@ -1550,16 +1260,6 @@ __device__ __forceinline__ void serial_tile(const Params& P, uint32_t blk, uint3
   uint32_t b0 = t0 % P.D;
   const bool skip_idle = skip_idle_on<Proto>() && !P.drop_ppm && !P.slow_ppm;
   for (uint32_t t = t0; t < t0 + nsteps; t++) {
-    if (PXS_PHASE_RECENT && P.phase_sort && t == t0 + nsteps / 2u)   // the launch's second half only
-      for (uint32_t k = 0; k < P.phase_period; k++) reinterpret_cast<uint32_t*>(x.l_cnt + P.ph_rel)[(k << 6) | x.lane] = 0;
-#ifndef PXS_STAMPS
-    if constexpr (lane_async<NT, Proto>()) {
-      const bool run = live && x.l_poison[x.lane] >= t;
-      x.t = t;
-      x.b0 = b0;
-      step_async<NT, Proto>(P, x, run ? replica_order<NT>(P, x, b0) : 0ull, run, img, L + (P.off_wscr - tail));
-    } else
-#endif
     if (live && x.l_poison[x.lane] >= t) {
       const uint64_t order = busy_first<NT, Proto>() ? replica_order<NT>(P, x, b0) : 0x0FEDCBA987654321ull;
 #pragma nounroll
@@ -1584,7 +1284,6 @@ __device__ __forceinline__ void serial_tile(const Params& P, uint32_t blk, uint3
 #endif
         const uint32_t flags0 = row_dirty_on<Proto>() ? x.flags : 0u, kvver0 = row_dirty_on<Proto>() ? x.kvver : 0u;
         Proto::template load<NT>(P, x);
-        if constexpr (Proto::step_scratch) Proto::template step_begin<NT>(P, x, L + (P.off_wscr - tail));
         rep_counters_zero<NT>(x);
 #ifdef PXS_STAMPS
         Stamps st = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1612,7 +1311,6 @@ __device__ __forceinline__ void serial_tile(const Params& P, uint32_t blk, uint3
           P.kv_ver[i] = x.kvver;
         }
         Proto::template store<NT>(P, x);
-        if constexpr (Proto::step_scratch) Proto::template step_end<NT>(P, x);
         rep_counters_flush<NT>(P, x);
       }
     }
@@ -1631,12 +1329,6 @@ __device__ __forceinline__ void serial_tile(const Params& P, uint32_t blk, uint3
         const uint32_t v = ph[(k << 6) | x.lane];
         if (v > most) { most = v; best = k; }
       }
-      // hysteresis: a cluster keeps its residue unless the new one leads it by
-      // more than PXS_PHASE_HYST percent, so near-ties do not move it back and forth
-      const uint32_t prev = P.phase[x.c];
-      if (PXS_PHASE_HYST && prev < P.phase_period && prev != best &&
-          most * 100u <= ph[(prev << 6) | x.lane] * (100u + PXS_PHASE_HYST))
-        best = prev;
       P.phase[x.c] = best;
     }
   }

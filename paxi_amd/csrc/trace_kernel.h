@@ -8,7 +8,7 @@
 // FIFO order - exactly what paxisim_read_inbox returns just before step t.
 //
 // The hook is trace_inbox, called where a replica-step reads its per-source
-// counts (sim_core.h replica_step and step_async): after client_start, so a late
+// counts (sim_core.h replica_step): after client_start, so a late
 // worker's first request is in the box, and before a crashed replica's discard
 // loop zeroes the counts, so the records socket.Recv throws away are in the
 // trace.  It runs before Proto::dispatch, so one site per loop form covers every

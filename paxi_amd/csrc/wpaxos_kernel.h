@@ -25,17 +25,8 @@
 
 namespace pxs {
 
-// The majority / ema policies run only on a leader's request path; built out
-// of line (PXS_POLICY_NOINLINE=1) they stay out of the merge loop's registers.
-#if defined(PXS_POLICY_NOINLINE) && PXS_POLICY_NOINLINE
-#define PXS_POLICY_FN __device__ __attribute__((noinline))
-#else
-#define PXS_POLICY_FN __device__ __forceinline__
-#endif
-
 template <int NT>
 __device__ __forceinline__ size_t wp_slot(const Params& P, const Rep<NT>& x, uint32_t key) {
-  if (PXS_WP_LANEMAJOR) return (((size_t)x.blk * nrep<NT>(P) + x.r) * LANES + x.lane) * P.keys + key;
   return (((size_t)x.blk * P.keys + key) * nrep<NT>(P) + x.r) * LANES + x.lane;
 }
 
@@ -122,9 +113,10 @@ __device__ __forceinline__ void wp_create(const Params& P, Rep<NT>& x) {
 }
 
 // majority.Hit (policy.go:79-93), the step as the clock; ids visited in index
-// order where Go ranges over a map, so the highest qualifying index wins
+// order where Go ranges over a map, so the highest qualifying index wins.
+// (Inline: the majority / ema policies built out of line cost config 5 8%, r1q.)
 template <int NT>
-PXS_POLICY_FN uint32_t majority_hit(uint4* q, uint32_t t, uint32_t id, uint32_t n, uint32_t interval) {
+__device__ __forceinline__ uint32_t majority_hit(uint4* q, uint32_t t, uint32_t id, uint32_t n, uint32_t interval) {
   const uint4 h0 = q[0], h1 = q[1];
   uint4 m = q[2];
   uint32_t w[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
@@ -155,7 +147,7 @@ PXS_POLICY_FN uint32_t majority_hit(uint4* q, uint32_t t, uint32_t id, uint32_t 
 // products go through an asm barrier.  Returns the new settled zone
 // (1-based), or 0.
 template <int NT>
-PXS_POLICY_FN uint32_t ema_hit(uint4* q, double alpha, double zid) {
+__device__ __forceinline__ uint32_t ema_hit(uint4* q, double alpha, double zid) {
   uint4 m = q[2];
   double s = __hiloint2double((int)m.y, (int)m.x);
   uint32_t res = 0;
@@ -243,19 +235,6 @@ __device__ __forceinline__ void wp_handle_request(const Params& P, Rep<NT>& x, u
   }
 }
 
-// Same-trip absorption of a P2b for the kpaxos still bound.
-//   0: off (default).
-//   1: the round-4 r4l experiment as DESIGN.md §5.6 describes it: the next
-//      P2b of the bound key runs p2b_absorb on the bound registers after the
-//      dispatch's unbind, and nothing writes them back again; nor is "bound"
-//      checked (load() leaves key 0 with another instance's registers).  A
-//      diagnostic build only: it loses HandleP2b's ballot adoption
-//      (paxos.go:281-284) whenever the absorbed P2b carries a higher ballot.
-//   2: the same absorption with an explicit bound key (none after load()) and
-//      the instance written back when the absorbed P2b changed ballot/active.
-// (the macro is defined in sim_core.h, whose merge loop calls absorb)
-constexpr uint32_t WP_UNBOUND = 0xFFFFu;   // x.key before the first bind of a replica-step (PXS_WP_ABSORB=2)
-
 // LDS: the instance scalars live in the tile's LDS image (wlds); else in HBM
 template <bool LDS>
 struct WPaxosProtoT {
@@ -270,55 +249,13 @@ struct WPaxosProtoT {
     x.e0 = 0;                        // entry of slot s: word 4*(s & (W-1)) of the lane's window
     x.es = 4;
     x.pstride = 1;
-    x.key = PXS_WP_ABSORB >= 2 ? WP_UNBOUND : 0u;
+    x.key = 0u;
     x.ktag = 0;
-  }
-  // HandleP2b (paxos.go:270-310) of a next message in the same trip, without
-  // a bind: only a P2b of the kpaxos whose registers are bound, and only when
-  // it completes no quorum (p2b_absorb).  handleAccepted (replica.go:90-93)
-  // first dereferences r.paxi[m.Key]: a nil kpaxos goes to the full handler,
-  // which poisons.
-  template <int NT>
-  __device__ static __forceinline__ bool absorb(const Params& P, Rep<NT>& x, uint32_t src, const uint4& m) {
-    if (hdr_type(m.x) != PAXISIM_MSG_P2B || hdr_key(m.x) != x.key || !x.exists) return false;
-    const uint32_t b0 = x.ballot, a0 = x.active;
-    if (!p2b_absorb<NT>(P, x, src, m)) return false;
-    if (PXS_WP_ABSORB >= 2 && (x.ballot != b0 || x.active != a0)) wp_unbind<NT, LDS>(P, x);
-    return true;
   }
   template <int NT>
   __device__ static __forceinline__ void store(const Params& P, const Rep<NT>& x) {
     PXS_TALLY_AT(P, x.blk, TC_ROW_ST, &P.nfwd[rc(P, x.r, x.c)], true);
     P.nfwd[rc(P, x.r, x.c)] = x.nfwd;
-  }
-  // The serial kernel (sim_core.h) runs one replica at a time: the instance
-  // scalars of that replica's K kpaxos move from the HBM image into an LDS
-  // scratch [key][word][lane] for its replica-step (one coalesced copy each
-  // way), so a bind / unbind is LDS traffic rather than eight keys' worth of
-  // scattered HBM rows per wave.
-  static constexpr bool step_scratch = LDS && PXS_WP_SCRATCH;
-  template <int NT>
-  __device__ static __forceinline__ void step_begin(const Params& P, Rep<NT>& x, uint8_t* scr) {
-    uint32_t* s = reinterpret_cast<uint32_t*>(scr);
-    const uint32_t* g = reinterpret_cast<const uint32_t*>(P.image + (size_t)x.blk * P.img.bytes + P.img.off_a) +
-                        ((x.r * WP_WORDS) << 6) + x.lane;
-    const uint32_t gk = (nrep<NT>(P) * WP_WORDS) << 6;
-    for (uint32_t k = 0; k < P.keys; k++)
-#pragma unroll
-      for (uint32_t w = 0; w < WP_WORDS; w++) s[((k * WP_WORDS + w) << 6) + x.lane] = g[k * gk + (w << 6)];
-    x.l_inst = s;
-    x.ikst = WP_WORDS << 6;
-    x.iro = 0;
-  }
-  template <int NT>
-  __device__ static __forceinline__ void step_end(const Params& P, const Rep<NT>& x) {
-    const uint32_t* s = x.l_inst;
-    uint32_t* g = reinterpret_cast<uint32_t*>(P.image + (size_t)x.blk * P.img.bytes + P.img.off_a) +
-                  ((x.r * WP_WORDS) << 6) + x.lane;
-    const uint32_t gk = (nrep<NT>(P) * WP_WORDS) << 6;
-    for (uint32_t k = 0; k < P.keys; k++)
-#pragma unroll
-      for (uint32_t w = 0; w < WP_WORDS; w++) g[k * gk + (w << 6)] = s[((k * WP_WORDS + w) << 6) + x.lane];
   }
   template <int NT>
   __device__ static __forceinline__ void client_request(const Params& P, Rep<NT>& x, uint32_t cid) {

@@ -63,7 +63,7 @@ def test_absorb_without_sdwa_peephole_matches_oracle():
 
 @pytest.mark.gpu
 def test_absorb_with_one_exit_send_matches_oracle():
-    """The source-level fix the product ships (sim_core.h PXS_SEND_ONE_EXIT):
+    """The source-level fix the product ships (sim_core.h send_begin):
     the pinned reproducer with the tree's one-exit send_begin in place of its
     early-return one does not diverge, with the same flags as the reproducer."""
     lib = ge.guard_lib("absorb_oneexit")
