@@ -93,7 +93,7 @@ struct LinClient {
 
 // Readout of one cluster (not part of the step): out[w * cap + j] is op j of
 // worker w in the checker's form, cnt[w] the worker's count (past cap: dropped).
-// One definition: the unit that launches it (paxisim.hip) asks for it.
+// One definition: the unit that launches it (host_check.hip) asks for it.
 #ifdef PXS_CHIST_READ
 __global__ void chist_read_kernel(Params P, uint64_t cl, uint4* out, uint32_t* cnt) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -61,7 +61,7 @@ __device__ __forceinline__ void lat_sample(const Params& P, uint32_t blk, uint32
 }
 
 // Readout: fold the slices into out[WK][bins + LAT_EXTRA] (not part of the step).
-// One definition: the unit that launches it (paxisim.hip) asks for it.
+// One definition: the unit that launches it (host_check.hip) asks for it.
 #ifdef PXS_LAT_REDUCE
 __global__ void lat_reduce(Params P, unsigned long long* out) {
   const size_t n = (size_t)P.WK * lat_row(P.lat_bins);

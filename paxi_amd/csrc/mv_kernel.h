@@ -47,7 +47,7 @@ __device__ __forceinline__ void mv_put(const Params& P, uint32_t key, uint32_t r
 }
 
 // The Consensus scan (not part of the step).  One definition: the unit that
-// launches it (paxisim.hip) asks for it.
+// launches it (host_check.hip) asks for it.
 #ifdef PXS_MV_SCAN
 constexpr uint32_t MV_WAVES = 4;        // waves per workgroup
 enum { MV_FAILED = 0, MV_VERSIONS, MV_DROPPED, MV_NOUT };

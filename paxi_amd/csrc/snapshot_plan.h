@@ -1,9 +1,10 @@
 // snapshot_plan.h — the host side of snapshot / restore / fork (host only, no HIP runtime calls):
 // the blob's header, the section-size arithmetic, the plan fingerprint and every validation
 // paxisim_restore and paxisim_snapshot_info perform (include/paxisim_snapshot.h has the format).
-// paxisim.hip runs these between its device calls; tests/snapshot_plan_check.cpp runs them without
-// a GPU.
+// host_snapshot.hip runs these between its device calls; tests/snapshot_plan_check.cpp runs them
+// without a GPU.
 #pragma once
+#include <array>
 #include <string>
 #include <vector>
 
@@ -13,7 +14,7 @@
 namespace pxs {
 
 constexpr uint32_t SNAP_NSEC = PAXISIM_SNAPSHOT_SECTIONS;
-constexpr uint32_t SNAP_LAT_SLICES = 8, SNAP_LAT_EXTRA = 4;   // = LAT_SLICES, LAT_EXTRA (lat_kernel.h; paxisim.hip asserts it)
+constexpr uint32_t SNAP_LAT_SLICES = 8, SNAP_LAT_EXTRA = 4;   // = LAT_SLICES, LAT_EXTRA (lat_kernel.h; host_snapshot.hip asserts it)
 constexpr uint32_t SNAP_CMP_WORDS = 8;                        // = CM_SUMS: a pool's compaction words before the block sums
 constexpr uint32_t SNAP_POOL_BYTES = 48;
 
@@ -82,6 +83,36 @@ inline void snap_sections(const Params& P, uint32_t policy, uint32_t n_plan_word
   out[PAXISIM_SNAP_MV] = r.mv_cap ? snap_mv_cnt_bytes(P) + snap_mv_val_bytes(P, r.mv_cap) : 0;
   out[PAXISIM_SNAP_TRACE] =
       r.tr_cap ? snap_tr_row_bytes(P) + snap_tr_cnt_bytes(P, r.tr_rows) + snap_tr_rec_bytes(P, r.tr_rows, r.tr_cap) : 0;
+}
+
+// The recorders' device buffers in snapshot order: the one list that snapshot, restore, fork, destroy
+// and paxisim_device_bytes walk, so a recorder added here is carried by all of them.  offset: the
+// buffer's place in its section; the TRACE section opens with the host-side tr_row table
+// (snap_tr_row_bytes), which is not a buffer of this list.  An absent recorder's entries have no bytes.
+struct SnapBuf {
+  uint32_t section;
+  void* ptr;
+  size_t bytes, offset;
+  bool present;
+};
+constexpr uint32_t SNAP_NBUF = 8;
+inline std::array<SnapBuf, SNAP_NBUF> snap_recorder_bufs(const Params& P, uint32_t tr_rows) {
+  const bool lat = P.lat_bins != 0, ch = P.ch_cap != 0, mv = P.mv_cap != 0, tr = P.tr_cap != 0;
+  std::array<SnapBuf, SNAP_NBUF> b = {{
+      {PAXISIM_SNAP_LAT, P.lat_stamp, snap_lat_stamp_bytes(P), 0, lat},
+      {PAXISIM_SNAP_LAT, P.lat_acc, snap_lat_acc_bytes(P, P.lat_bins), 0, lat},
+      {PAXISIM_SNAP_CHIST, P.ch_cnt, snap_ch_cnt_bytes(P), 0, ch},
+      {PAXISIM_SNAP_CHIST, P.ch_ops, snap_ch_ops_bytes(P, P.ch_cap), 0, ch},
+      {PAXISIM_SNAP_MV, P.mv_cnt, snap_mv_cnt_bytes(P), 0, mv},
+      {PAXISIM_SNAP_MV, P.mv_val, snap_mv_val_bytes(P, P.mv_cap), 0, mv},
+      {PAXISIM_SNAP_TRACE, P.tr_cnt, snap_tr_cnt_bytes(P, tr_rows), snap_tr_row_bytes(P), tr},
+      {PAXISIM_SNAP_TRACE, P.tr_rec, snap_tr_rec_bytes(P, tr_rows, P.tr_cap), 0, tr},
+  }};
+  for (uint32_t i = 0; i < SNAP_NBUF; i++) {
+    if (!b[i].present) b[i].bytes = 0;
+    if (i && b[i].section == b[i - 1].section) b[i].offset = b[i - 1].offset + b[i - 1].bytes;
+  }
+  return b;
 }
 
 // ---- the plan fingerprint ---------------------------------------------------------------------

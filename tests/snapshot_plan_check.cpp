@@ -5,9 +5,10 @@
 // compares every section size and offset with carve_arena's and the recorders' own arithmetic, and
 // on whole blobs exercises every refusal: each truncation point, bad magic, bad version, every
 // section size off by one, a foreign build id, every fingerprint word changed alone, every
-// recorder mismatch.
+// recorder mismatch.  The list of the recorders' device buffers is checked against the section sizes.
 #include <cinttypes>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "snapshot_plan.h"
@@ -324,9 +325,52 @@ static void refusals() {
   }
 }
 
+// snap_recorder_bufs, the list snapshot / restore / fork / destroy walk, against snap_sections: every
+// recorder on and off, alone and together, at two shapes.  The pointers are made up; nothing reads them.
+static void recorder_table() {
+  for (const uint32_t N : {3u, 9u}) {
+    const Shape s = shape(PAXISIM_PAXOS, N, 4, 16, 130);
+    CHECK(s.ok, "shape N %u", N);
+    for (uint32_t on = 0; on < 16; on++) {
+      Params P = s.P;
+      const uint32_t tr_rows = 2;
+      uintptr_t next = 0x1000;
+      auto fake = [&](auto*& p) { p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(next += 0x1000); };
+      if (on & 1) { P.lat_bins = 16; fake(P.lat_stamp); fake(P.lat_acc); }
+      if (on & 2) { P.ch_cap = 8; fake(P.ch_cnt); fake(P.ch_ops); }
+      if (on & 4) { P.mv_cap = 4; fake(P.mv_cnt); fake(P.mv_val); }
+      if (on & 8) { P.tr_cap = 32; P.tr_from = 0; P.tr_to = 96; fake(P.tr_cnt); fake(P.tr_rec); }
+      uint64_t sec[SNAP_NSEC];
+      snap_sections(P, s.cfg.policy, 90, 0, 1, snap_recorders(P, tr_rows), 0, sec);
+      const auto bufs = snap_recorder_bufs(P, tr_rows);
+      const void* const want[SNAP_NBUF] = {P.lat_stamp, P.lat_acc, P.ch_cnt, P.ch_ops, P.mv_cnt, P.mv_val, P.tr_cnt, P.tr_rec};
+      const uint32_t section[SNAP_NBUF] = {PAXISIM_SNAP_LAT, PAXISIM_SNAP_LAT, PAXISIM_SNAP_CHIST, PAXISIM_SNAP_CHIST,
+                                           PAXISIM_SNAP_MV, PAXISIM_SNAP_MV, PAXISIM_SNAP_TRACE, PAXISIM_SNAP_TRACE};
+      uint64_t sum[SNAP_NSEC] = {0};
+      for (uint32_t i = 0; i < SNAP_NBUF; i++) {
+        const SnapBuf& b = bufs[i];
+        const bool present = (on >> (i / 2)) & 1u;
+        const uint64_t lead = b.section == PAXISIM_SNAP_TRACE ? snap_tr_row_bytes(P) : 0;   // the host-side tr_row table
+        CHECK(b.section == section[i] && b.ptr == want[i], "N %u on %u: entry %u is section %u", N, on, i, b.section);
+        CHECK(b.present == present && (b.ptr != nullptr) == present && (b.bytes != 0) == present,
+              "N %u on %u: entry %u present %d, %zu bytes", N, on, i, (int)b.present, b.bytes);
+        CHECK(b.offset == lead + sum[b.section], "N %u on %u: entry %u at offset %zu", N, on, i, b.offset);
+        sum[b.section] += b.bytes;
+      }
+      for (const uint32_t k : {(uint32_t)PAXISIM_SNAP_LAT, (uint32_t)PAXISIM_SNAP_CHIST, (uint32_t)PAXISIM_SNAP_MV})
+        CHECK(sum[k] == sec[k], "N %u on %u: section %u is %" PRIu64 " bytes, the table's buffers %" PRIu64, N, on, k, sec[k], sum[k]);
+      const uint64_t lead = (on & 8) ? snap_tr_row_bytes(P) : 0;
+      CHECK(sum[PAXISIM_SNAP_TRACE] == sec[PAXISIM_SNAP_TRACE] - lead,
+            "N %u on %u: trace section %" PRIu64 " bytes, tr_row %" PRIu64 ", the table's buffers %" PRIu64, N, on,
+            sec[PAXISIM_SNAP_TRACE], lead, sum[PAXISIM_SNAP_TRACE]);
+    }
+  }
+}
+
 int main() {
   grid();
   refusals();
+  recorder_table();
   if (g_fail) {
     std::printf("%d failures in %ld checks\n", g_fail, g_checks);
     return 1;

@@ -423,6 +423,49 @@ def test_fork():
     o.close()
 
 
+# ---- every recorder at once --------------------------------------------------------------------------
+def test_all_four_recorders_through_restore_and_fork():
+    """Latency, client history, multiversion and trace on one handle: the one list of recorder buffers
+    (snapshot_plan.h) carries all eight through snapshot -> restore and through fork.  48 steps, then
+    48 more; the restored and the forked handle equal the one stepped straight through in every
+    readout, the traced rows and the device bytes included."""
+    traced, steps = (3, 64), 48
+
+    def new():
+        s = make("paxos5", recorders=dict(lat=16, chist=8, mv=4))
+        s.trace_enable(traced, 32)
+        return s
+
+    def out(s):
+        d = readout(s)
+        d["trace"] = [s.trace_read(c, r) for c in traced for r in range(s.N)]
+        d["trace_totals"] = s.trace_totals()
+        d["device_bytes"] = s.device_bytes()
+        return d
+
+    a = new()
+    a.step(2 * steps)
+    want = out(a)
+    a.close()
+    # every recorder has recorded something
+    assert want["trace_totals"][0] > 0 and want["lat"][1] > 0 and want["consensus"][1] > 0
+    assert any(ops for ops, _ in want["chist"])
+
+    b = new()
+    b.step(steps)
+    blob = b.snapshot()
+    f = b.fork()
+    f._rec = b._rec
+    b.close()
+    assert snapshot.info(blob)["recorders"] == {"latency": True, "client_history": True, "multiversion": True, "trace": True}
+    r = new()
+    r.restore(blob)
+    for s, ctx in ((r, "restored"), (f, "forked")):
+        s.step(steps)
+        same(want, out(s), f"all four recorders, {ctx}")
+        s.close()
+
+
 # ---- rewind and trace --------------------------------------------------------------------------------
 def test_rewind_and_trace():
     cfg, wl, fp, faults = trace_ref.paxos_case()

@@ -96,7 +96,7 @@ def test_client_history_overflows_in_some_clusters_only():
 
 def test_no_step_unit_includes_the_changed_headers():
     """The verdict kernels and the per-cluster marks of the linearizability scan live in headers that
-    only paxisim.hip includes, so no step kernel is compiled from different text."""
+    only host_check.hip includes, so no step kernel is compiled from different text."""
     import __graft_entry__ as ge
     for src in ge.HIP_SOURCES:
         if src.startswith("k_"):
