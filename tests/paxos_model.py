@@ -28,7 +28,9 @@ change nothing; POISON appears exactly where Go panics.
 `replay`, `words_of` and `check_end` also serve the per-key protocols (tests/wpaxos_model.py,
 DESIGN.md §3.5g): `replay` takes a replica factory, `words_of` accepts the key tag of P1a..P3 and
 LeaderChange there, and `check_end` then compares every (replica, key) instance of read_instances
-and its window, and read_state's aggregates over them.
+and its window, and read_state's aggregates over them.  ABD (tests/abd_model.py)
+uses `replay`, `Client`, `crash_windows` and the leftover-sends rule (`check_leftovers`) with a
+check of the end of its own; `words_of` holds its records to ABD's framing.
 
 Simulator plumbing, not protocol, and shared with tests/epaxos_model.py: mix64 / fmix32 and the
 merge order of a step's inbox (`handled`).  Record encodings are those of DESIGN.md §3.1-3.2; the
@@ -48,6 +50,9 @@ SOCKET_TYPES = (T_REQUEST, T_REPLY, T_P1A, T_P1B, T_P2A, T_P2B, T_P3)
 # the per-key protocols (tests/wpaxos_model.py): kpaxos.Broadcast / Send tag P1a..P3 with the key
 # (hdr bits 16-31); Requests and Replies stay untagged; WPaxos and M2Paxos add LeaderChange
 KEYED_TYPES = (T_P1A, T_P1B, T_P2A, T_P2B, T_P3, T_LEADERCHG)
+# ABD (tests/abd_model.py): hdr = type | key << 8, one record per message; a Request comes from the client only
+T_GET, T_GETREPLY, T_SET, T_SETREPLY = trace.T_GET, trace.T_GETREPLY, trace.T_SET, trace.T_SETREPLY
+ABD_TYPES = (T_GET, T_GETREPLY, T_SET, T_SETREPLY)
 CLIENT = abi.CLIENT_SRC
 
 
@@ -425,12 +430,14 @@ class Client:
         self.cur = [1 + w for w in range(self.WK)]
         self.issued = [1] * self.WK
         self.due = {(wl.start_step[w], wl.target[w], 1 + w) for w in range(self.WK)}
+        self.reply_value = [0] * self.WK                   # Reply.Value of the worker's last answered request
         self.step = 0
 
     def reply(self, cid, value):
         w = (cid - 1) % self.WK
         if self.cur[w] != cid:
             return False
+        self.reply_value[w] = value
         if self.wl.max_requests == 0 or self.issued[w] < self.wl.max_requests:
             self.cur[w] = 1 + w + self.WK * self.issued[w]
             self.issued[w] += 1
@@ -446,12 +453,17 @@ class Client:
         self.due.remove((t, dst, cid))
 
 
-def words_of(recs, keys=0):
+def words_of(recs, keys=0, abd=False):
     """One traced message -> its words, after checking its framing: only a P1b carries payload
     records, as many as its header says, each a P1B_ENTRY.  Multi-Paxos (keys = 0) has no key tag
     and no LeaderChange; of a per-key protocol's messages P1a..P3 and LeaderChange carry a key
-    below `keys`, Requests and Replies none."""
+    below `keys`, Requests and Replies none.  ABD: hdr = type | key << 8 with the key below `keys`,
+    one record per message, no payload; its only other record is the client's Request."""
     hdr = recs[0][1]
+    if abd:
+        assert hdr == T_REQUEST or (hdr & 0xFF in ABD_TYPES and hdr >> 8 < keys), f"header of {recs}"
+        assert len(recs) == 1, f"framing of {recs}"
+        return tuple(recs[0][1:])
     t, n = hdr & 0xFF, (hdr >> 8) & 0xFF
     if keys and t in KEYED_TYPES:
         assert hdr >> 16 < keys, f"key tag of {recs}"
@@ -480,7 +492,8 @@ def replay(msgs, cfg, wl, gid, command_of, crashes=(), injected=(), delivered_in
     paxisim_inject; `delivered_in` {(step, src, dst, words)} of paxisim_deliver.  `make_replica`
     (index, cfg, client, command_of) builds one model replica: `Replica`, or a per-key one."""
     N, D = abi.n_replicas(cfg), cfg.max_delay
-    keys = cfg.keys if cfg.protocol in abi.PER_KEY else 0
+    abd = cfg.protocol == abi.ABD
+    keys = cfg.keys if abd or cfg.protocol in abi.PER_KEY else 0
     kc = mix64(cfg.seed ^ mix64((gid + 0x9E3779B97F4A7C15) & M64)) & M32
     client = Client(wl)
     reps = [make_replica(r, cfg, client, command_of) for r in range(N)]
@@ -511,12 +524,12 @@ def replay(msgs, cfg, wl, gid, command_of, crashes=(), injected=(), delivered_in
         if any(r == dst and a <= t < b for (r, a, b) in crashes):        # socket.Recv discards (socket.go:111-118)
             for src in [s for s in by_src if s < N]:
                 for recs in by_src.pop(src):
-                    matched += match(t, src, dst, words_of(recs, keys))
+                    matched += match(t, src, dst, words_of(recs, keys, abd))
                     me.discarded += 1
         step_key = fmix32(kc ^ ((t * 0x9E3779B1) & M32))
         dead = False
         for src, recs in handled(step_key, dst, by_src, N + 1):
-            words = words_of(recs, keys)
+            words = words_of(recs, keys, abd)
             if src == N:
                 assert words[0] == T_REQUEST and words[1:3] == (0, 0), f"client record {recs}"
                 if (t, dst, words[3]) not in injected:
@@ -602,6 +615,28 @@ def check_keyed(sim, c, r, m, st, ins, cfg):
                         f"pending, digest chain) {got} against the model's {want}"
 
 
+def check_leftovers(rp, states, c, steps, drains, D):
+    """The sends nobody received against `dropped`, and the client's requests against the trace."""
+    left = [(te, k, w) for k, v in rp.unmatched.items() for (te, w) in v]
+    if rp.panics:
+        # the cluster is frozen after the panic's step: the leftovers are held against `dropped` as
+        # those of a run of that many steps that does not drain
+        assert rp.last_step <= rp.panics[0][0]
+        steps, drains = rp.panics[0][0] + 1, False
+    else:
+        due = [d for d in rp.client.due if d[0] < steps]
+        assert not due, f"cluster {c}: requests the model's client sent and the trace lacks: {sorted(due)[:3]}"
+    dropped = sum(s.dropped for s in states)
+    if drains:
+        assert rp.last_step < steps - 1 - D, "the run has not drained"
+        assert len(left) == dropped, f"cluster {c}: {len(left)} sends nobody received, {dropped} dropped"
+    else:
+        # a leftover is a dropped send or still on its way: none dropped, none old; and never more
+        # old ones than were dropped, nor more dropped than are left
+        late = [x for x in left if steps - x[0] > 1 + D]
+        assert len(late) <= dropped <= len(left), f"cluster {c}: {dropped} dropped, never delivered: {late[:3]}"
+
+
 def check_end(rp, sim, c, cfg, steps, drains):
     """The end of a replayed cluster c against read_state / read_log (a per-key protocol: and
     read_instances) of `sim`, and the sends nobody received.  Returns the cluster's flag word."""
@@ -631,30 +666,14 @@ def check_end(rp, sim, c, cfg, steps, drains):
             assert st.flags & abi.F_WOVF, f"cluster {c} replica {r}: an entry beyond the window, and no WOVF"
         if any(s < p.execute for p in ps for s in p.log):
             assert st.flags & abi.F_GHOST, f"cluster {c} replica {r}: an entry below execute, and no GHOST"
-    left = [(te, k, w) for k, v in rp.unmatched.items() for (te, w) in v]
-    if rp.panics:
-        # the cluster is frozen after the panic's step: the leftovers are held against `dropped` as
-        # those of a run of that many steps that does not drain
-        assert rp.last_step <= rp.panics[0][0]
-        steps, drains = rp.panics[0][0] + 1, False
-    else:
-        due = [d for d in rp.client.due if d[0] < steps]
-        assert not due, f"cluster {c}: requests the model's client sent and the trace lacks: {sorted(due)[:3]}"
-    dropped = sum(s.dropped for s in states)
-    if drains:
-        assert rp.last_step < steps - 1 - D, "the run has not drained"
-        assert len(left) == dropped, f"cluster {c}: {len(left)} sends nobody received, {dropped} dropped"
-    else:
-        # a leftover is a dropped send or still on its way: none dropped, none old; and never more
-        # old ones than were dropped, nor more dropped than are left
-        late = [x for x in left if steps - x[0] > 1 + D]
-        assert len(late) <= dropped <= len(left), f"cluster {c}: {dropped} dropped, never delivered: {late[:3]}"
+    check_leftovers(rp, states, c, steps, drains, D)
     return word
 
 
-def replay_cluster(sim, sh, c, msgs, injected=(), delivered_in=(), make_replica=Replica):
+def replay_cluster(sim, sh, c, msgs, injected=(), delivered_in=(), make_replica=Replica, check=None):
     """Replay traced cluster c of a finished run of shape `sh` on `sim` (the oracle or the device)
-    and check its end.  Returns the Replay and the cluster's flag word."""
+    and check its end (`check`: check_end, or a protocol's own with its arguments).  Returns the
+    Replay and the cluster's flag word."""
     cfg = sh.cfg
     memo = {}
 
@@ -666,7 +685,7 @@ def replay_cluster(sim, sh, c, msgs, injected=(), delivered_in=(), make_replica=
 
     rp = replay(msgs, cfg, sh.wl, cfg.cluster_base + c, command_of, crash_windows(sh.faults, cfg.cluster_base + c),
                 injected, delivered_in, make_replica)
-    return rp, check_end(rp, sim, c, cfg, sh.steps, sh.drains)
+    return rp, (check or check_end)(rp, sim, c, cfg, sh.steps, sh.drains)
 
 
 # ---- the shapes shared by the CPU and GPU suites (tests/test_paxos_model.py, test_paxos_model_gpu.py)
