@@ -239,25 +239,7 @@ class Stats(C.Structure):
         return d
 
 
-# C prototypes of the multi-version Database calls, every one returning int:
-# the product library only, bound where a library has them (paxi_amd.sim.load_library).
-MV_PROTOTYPES = {
-    "paxisim_multiversion_enable": [C.c_void_p, C.c_uint32],
-    "paxisim_kv_history": [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32,
-                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
-    "paxisim_consensus": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
-    "paxisim_consensus_failed": [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)],
-}
-
-# C prototypes of the device message trace, likewise
-TRACE_PROTOTYPES = {
-    "paxisim_trace_enable": [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32],
-    "paxisim_trace_read": [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(TraceRecord), C.c_uint32,
-                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
-    "paxisim_trace_totals": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
-}
-
-# Snapshot, restore and fork (include/paxisim_snapshot.h), likewise
+# Snapshot, restore and fork (include/paxisim_snapshot.h)
 SNAPSHOT_SECTIONS = ("plan", "faults", "pools", "arena", "mailbox", "lat", "chist", "mv", "trace")
 SNAPSHOT_HEADER = 256
 SNAP_HAS_LAT, SNAP_HAS_CHIST, SNAP_HAS_MV, SNAP_HAS_TRACE = 1, 2, 4, 8
@@ -272,16 +254,8 @@ class SnapshotInfo(C.Structure):
                 ("build_id", C.c_char * 32)]
 
 
-SNAPSHOT_PROTOTYPES = {
-    "paxisim_snapshot_size": [C.c_void_p, C.POINTER(C.c_uint64)],
-    "paxisim_snapshot": [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)],
-    "paxisim_restore": [C.c_void_p, C.c_void_p, C.c_uint64],
-    "paxisim_fork": [C.c_void_p, C.POINTER(C.c_void_p)],
-    "paxisim_snapshot_info": [C.c_void_p, C.c_uint64, C.POINTER(SnapshotInfo)],
-}
-
-# Per-cluster verdict words and the search over them (include/paxisim_verdict.h),
-# likewise.  Bits 0..7 of a word are the F_* flags above.
+# Per-cluster verdict words and the search over them (include/paxisim_verdict.h).
+# Bits 0..7 of a word are the F_* flags above.
 V_FLAGS = 0xFF
 V_AGREE, V_CONSENSUS, V_LIN, V_CLIENT_LIN, V_LIN_SKIPPED, V_TRUNCATED = (1 << b for b in range(8, 14))
 V_QUIET, V_WAITING, V_STALLED = (1 << b for b in range(16, 19))
@@ -292,45 +266,149 @@ V_NAMES = {0: "WOVF", 1: "GHOST", 2: "MBOX_OVF", 3: "PEND_OVF", 4: "UNFAITHFUL",
            7: "HIST_OVF", 8: "AGREE", 9: "CONSENSUS", 10: "LIN", 11: "CLIENT_LIN", 12: "LIN_SKIPPED",
            13: "TRUNCATED", 16: "QUIET", 17: "WAITING", 18: "STALLED"}
 
-VERDICT_PROTOTYPES = {
-    "paxisim_verdict_available": [C.c_void_p, C.POINTER(C.c_uint32)],
-    "paxisim_verdicts": [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p],
-    "paxisim_find": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)],
-    "paxisim_verdict_counts": [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)],
-    "paxisim_select_words": [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
-                             C.POINTER(C.c_uint64)],
-}
-
 
 # enum paxisim_unit (include/paxisim_shape.h): what Simulation.step_unit returns
 UNIT_GENERIC, UNIT_FIXED_PAXOS5 = 0, 1
 
 
-# C prototypes shared by the product library (prefix "paxisim") and the oracle ("oracle").
+class PaxisimError(RuntimeError):
+    pass
+
+
+# The C prototypes, name -> (restype, argtypes): the binding's single source, in the headers' own
+# types (tests/test_abi.py compares every entry with include/*.h and oracle/oracle.h).  A handle
+# (paxisim*, paxisim_dist*, oracle_sim*) and void* are c_void_p.
+_P, _h, _int, _u32, _u64, _dbl = C.POINTER, C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_double
+_pu32, _pu64 = _P(_u32), _P(_u64)
+
+# calls the product library ("paxisim_") and the tests' CPU oracle ("oracle_") both have
+_SHARED = {
+    "create": (_int, [_P(Config), _P(Workload), _P(FaultProcess), _P(_h)]),
+    "destroy": (_int, [_h]),
+    "fault_add": (_int, [_h, _P(Fault)]),
+    "stats_get": (_int, [_h, _P(Stats)]),
+    "read_state": (_int, [_h, _u64, _u64, _P(ReplicaState)]),
+    "read_instances": (_int, [_h, _u64, _u64, _P(InstanceState)]),
+    "check": (_int, [_h, _pu64]),
+    "inject": (_int, [_h, _u64, _u32, _u32]),
+    "read_inbox": (_int, [_h, _u64, _u32, _P(InboxRecord), _u32, _pu32]),
+    "deliver": (_int, [_h, _u64, _u32, _u32, _P(InboxRecord), _u32]),
+    "read_log": (_int, [_h, _u64, _u32, _u32, C.c_int32, _u32, _P(LogEntry)]),
+    "read_client": (_int, [_h, _u64, _P(WorkerState), _u32, _pu32]),
+    "history": (_int, [_h, _u64, _pu32, _u32, _pu32]),
+    "history_load": (_int, [_h, _u64, _u32, _pu32, _u32]),
+    "read_kv": (_int, [_h, _u64, _u32, _pu32, _u32]),
+    "last_error": (C.c_char_p, []),
+}
+PROTOTYPES = {f"{prefix}_{name}": proto for prefix in ("paxisim", "oracle") for name, proto in _SHARED.items()}
+PROTOTYPES.update({
+    "paxisim_abi_version": (_int, []),
+    "paxisim_build_id": (C.c_char_p, []),
+    "paxisim_step": (_int, [_h, _u32]),
+    "paxisim_sync": (_int, [_h]),
+    "paxisim_commands": (_int, [_h, _u64, _pu32, _u32, _pu32, _pu32]),
+    "paxisim_kernel_time": (_int, [_h, _P(_dbl), _pu64, _int]),
+    "paxisim_linearizable": (_int, [_h, _pu64, _pu64, _pu64]),
+    "paxisim_occupancy": (_int, [_h, _P(_int), _pu32, _pu32]),
+    "paxisim_active_clusters": (_int, [_h, _pu64]),
+    "paxisim_read_activity": (_int, [_h, _u64, _u64, _pu32]),
+    "paxisim_quorum": (_int, [_P(Config), _u32, _u32, _P(_int)]),
+    "paxisim_device_bytes": (_int, [_h, _pu64]),
+    # client request latency
+    "paxisim_latency_enable": (_int, [_h, _u32]),
+    "paxisim_latency_reset": (_int, [_h]),
+    "paxisim_latency_get": (_int, [_h, _u32, _P(Latency), _pu64]),
+    "paxisim_latency_stat_of": (_int, [_P(Latency), _pu64, _dbl, _P(LatencyStat)]),
+    # the client-side op history of every protocol (§3.13)
+    "paxisim_client_history_enable": (_int, [_h, _u32]),
+    "paxisim_client_history": (_int, [_h, _u64, _pu32, _u32, _pu32, _pu32]),
+    "paxisim_client_history_load": (_int, [_h, _u64, _u32, _pu32, _u32]),
+    "paxisim_client_linearizable": (_int, [_h, _pu64, _pu64, _pu64]),
+    # the multi-version Database and Consensus (§3.14)
+    "paxisim_multiversion_enable": (_int, [_h, _u32]),
+    "paxisim_kv_history": (_int, [_h, _u64, _u32, _u32, _pu32, _u32, _pu32, _pu32]),
+    "paxisim_consensus": (_int, [_h, _pu64, _pu64, _pu64]),
+    "paxisim_consensus_failed": (_int, [_h, _u64, _u64, _pu64]),
+    # the device message trace (§3.15)
+    "paxisim_trace_enable": (_int, [_h, _pu64, _u32, _u32, _u32, _u32]),
+    "paxisim_trace_read": (_int, [_h, _u64, _u32, _P(TraceRecord), _u32, _pu32, _pu32]),
+    "paxisim_trace_totals": (_int, [_h, _pu64, _pu64]),
+    # RCCL reduction of statistics over handles
+    "paxisim_dist_init": (_int, [_P(_h), _int, _P(_h)]),
+    "paxisim_dist_unique_id": (_int, [C.c_char_p]),
+    "paxisim_dist_init_rank": (_int, [_h, C.c_char_p, _int, _int, _P(_h)]),
+    "paxisim_dist_allreduce": (_int, [_h, _pu64, _u32, _P(_dbl), _u32, _pu64, _P(_dbl)]),
+    "paxisim_dist_stats": (_int, [_h, _P(Stats), _P(_dbl)]),
+    "paxisim_dist_destroy": (_int, [_h]),
+    # snapshot, restore and fork (include/paxisim_snapshot.h, §3.16)
+    "paxisim_snapshot_size": (_int, [_h, _pu64]),
+    "paxisim_snapshot": (_int, [_h, _h, _u64, _pu64]),
+    "paxisim_restore": (_int, [_h, _h, _u64]),
+    "paxisim_fork": (_int, [_h, _P(_h)]),
+    "paxisim_snapshot_info": (_int, [_h, _u64, _P(SnapshotInfo)]),
+    # per-cluster verdict words and the search over them (include/paxisim_verdict.h, §3.17)
+    "paxisim_verdict_available": (_int, [_h, _pu32]),
+    "paxisim_verdicts": (_int, [_h, _u32, _u64, _u64, _pu32]),
+    "paxisim_find": (_int, [_h, _u32, _u32, _u32, _pu64, _u64, _pu64]),
+    "paxisim_verdict_counts": (_int, [_h, _u32, _pu64]),
+    "paxisim_select_words": (_int, [_int, _pu32, _u64, _u32, _u32, _pu64, _u64, _pu64]),
+    # which step-kernel unit a handle runs (include/paxisim_shape.h, §5.20)
+    "paxisim_step_unit": (_int, [_h, _pu32]),
+    # the oracle's own
+    "oracle_step": (_int, [_h, _u32, _int]),
+    "oracle_set_replica_order": (_int, [_h, _u32]),
+    "oracle_exec_log": (_int, [_h, _u64, _u32, _pu32, _u32, _pu32]),
+    "oracle_lin_check": (_int, [_h, _pu64, _pu64]),
+    "oracle_command": (_int, [_h, _u64, _u32, _pu32, _pu32]),
+    "oracle_new_ballot": (_u64, [_u32, _u32, _u32]),
+    "oracle_ballot_next": (_u64, [_u64, _u32, _u32]),
+    "oracle_quorum": (_int, [_u32, _u32, _u32, _pu32, _u32]),
+    "oracle_linearizable": (_int, [_P(C.c_int64), _int]),
+})
+# the two calls only an instrumented build has (paxisim.hip, in no header): tools/ bind them too
+DEBUG_PROTOTYPES = {
+    "paxisim_dbg_enable": (_int, [_h]),
+    "paxisim_dbg_read": (_int, [_h, _P(C.c_ulonglong)]),
+}
+
+
+class Bound:
+    """A loaded library's calls of one prefix, each under its table prototype, as attributes by
+    full name and by the name without the prefix (`L.paxisim_check` is `L.check`).  A library built
+    from older sources (the miscompile guard's pinned reproducers) lacks the newer calls: they are
+    listed in `missing`, and looking one up raises PaxisimError.  That holds for hasattr(L, name)
+    and getattr(L, name, None) too, which only catch AttributeError: ask `name in L.missing`."""
+
+    def __init__(self, lib, prefix, table):
+        self.lib, self.prefix, self.missing = lib, prefix, []
+        for name, (res, args) in table.items():
+            if not name.startswith(prefix + "_"):
+                continue
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                self.missing.append(name)
+                continue
+            fn.restype, fn.argtypes = res, args
+            self.__dict__[name] = self.__dict__[name[len(prefix) + 1:]] = fn
+
+    def __getattr__(self, name):  # only reached for a name that __init__ did not bind
+        d = self.__dict__                # empty before __init__ ran (copy, pickle): no lookups on self
+        full = name if name.startswith(d.get("prefix", "") + "_") else f"{d.get('prefix')}_{name}"
+        if full in d.get("missing", ()):
+            raise PaxisimError(f"{d['lib']._name} was built without {full}")
+        raise AttributeError(name)
+
+
+def bind(lib, prefix, table=PROTOTYPES):
+    """Give every `prefix`_ call of `table` that the ctypes library `lib` exports its prototype."""
+    return Bound(lib, prefix, table)
+
+
 def declare(lib, prefix):
-    P = C.POINTER
-    h = C.c_void_p
-    spec = {
-        "create": (C.c_int, [P(Config), P(Workload), P(FaultProcess), P(h)]),
-        "destroy": (C.c_int, [h]),
-        "fault_add": (C.c_int, [h, P(Fault)]),
-        "stats_get": (C.c_int, [h, P(Stats)]),
-        "read_state": (C.c_int, [h, C.c_uint64, C.c_uint64, P(ReplicaState)]),
-        "read_instances": (C.c_int, [h, C.c_uint64, C.c_uint64, P(InstanceState)]),
-        "check": (C.c_int, [h, P(C.c_uint64)]),
-        "inject": (C.c_int, [h, C.c_uint64, C.c_uint32, C.c_uint32]),
-        "read_log": (C.c_int, [h, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, P(LogEntry)]),
-        "history_load": (C.c_int, [h, C.c_uint64, C.c_uint32, P(C.c_uint32), C.c_uint32]),
-        "read_kv": (C.c_int, [h, C.c_uint64, C.c_uint32, P(C.c_uint32), C.c_uint32]),
-        "read_inbox": (C.c_int, [h, C.c_uint64, C.c_uint32, P(InboxRecord), C.c_uint32, P(C.c_uint32)]),
-        "deliver": (C.c_int, [h, C.c_uint64, C.c_uint32, C.c_uint32, P(InboxRecord), C.c_uint32]),
-        "last_error": (C.c_char_p, []),
-    }
-    for name, (res, args) in spec.items():
-        fn = getattr(lib, f"{prefix}_{name}")
-        fn.restype = res
-        fn.argtypes = args
-    return lib
+    """bind() for a loader that keeps the ctypes library itself and returns it: the prototypes sit on
+    lib's own function objects.  A call lib lacks is then ctypes' AttributeError, not PaxisimError."""
+    return bind(lib, prefix).lib
 
 
 def make_config(npz=(5,), protocol=PAXOS, q1=Q_MAJORITY, q2=Q_MAJORITY, fz=0, thrifty=0,

@@ -16,10 +16,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # PAXISIM_LIB selects another build of the same HIP library (tuning variants)
 LIB_PATH = os.environ.get("PAXISIM_LIB") or os.path.join(_HERE, "libpaxisim.so")
 _lib = None
-
-
-class PaxisimError(RuntimeError):
-    pass
+_PU32, _PU64 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)   # what the numpy-buffer wrappers hand over
+PaxisimError = abi.PaxisimError
+# every call include/*.h declares: the product's names of the one prototype table
+EXPORTED = [name for name in abi.PROTOTYPES if name.startswith("paxisim_")]
 
 
 def quorum(cfg, kind, ack_mask):
@@ -30,108 +30,14 @@ def quorum(cfg, kind, ack_mask):
 
 
 def load_library():
-    """Load the in-tree HIP library; raise if it is absent (no fallback)."""
+    """Load the in-tree HIP library, bound by abi.PROTOTYPES; raise if it is absent (no fallback).
+    A call the library lacks raises PaxisimError where it is looked up (abi.Bound)."""
     global _lib
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
         raise PaxisimError(f"HIP library not built: {LIB_PATH} (run `python -c 'import __graft_entry__ as g; g.build()'`)")
-    L = C.CDLL(LIB_PATH)
-    abi.declare(L, "paxisim")
-    L.paxisim_abi_version.restype = C.c_int
-    L.paxisim_build_id.restype = C.c_char_p
-    L.paxisim_build_id.argtypes = []
-    L.paxisim_step.restype = C.c_int
-    L.paxisim_step.argtypes = [C.c_void_p, C.c_uint32]
-    L.paxisim_sync.restype = C.c_int
-    L.paxisim_sync.argtypes = [C.c_void_p]
-    L.paxisim_kernel_time.restype = C.c_int
-    L.paxisim_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
-    L.paxisim_linearizable.restype = C.c_int
-    L.paxisim_linearizable.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
-                                       C.POINTER(C.c_uint64)]
-    L.paxisim_history.restype = C.c_int
-    L.paxisim_history.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint32,
-                                  C.POINTER(C.c_uint32)]
-    L.paxisim_occupancy.restype = C.c_int
-    L.paxisim_occupancy.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    L.paxisim_active_clusters.restype = C.c_int
-    L.paxisim_active_clusters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    L.paxisim_quorum.restype = C.c_int
-    L.paxisim_quorum.argtypes = [C.POINTER(abi.Config), C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]
-    L.paxisim_read_client.restype = C.c_int
-    L.paxisim_read_client.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(abi.WorkerState), C.c_uint32,
-                                      C.POINTER(C.c_uint32)]
-    L.paxisim_read_activity.restype = C.c_int
-    L.paxisim_read_activity.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]
-    L.paxisim_device_bytes.restype = C.c_int
-    L.paxisim_device_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    P = C.POINTER
-    L.paxisim_dist_init.restype = C.c_int
-    L.paxisim_dist_init.argtypes = [P(C.c_void_p), C.c_int, P(C.c_void_p)]
-    L.paxisim_dist_unique_id.restype = C.c_int
-    L.paxisim_dist_unique_id.argtypes = [C.c_char_p]
-    L.paxisim_dist_init_rank.restype = C.c_int
-    L.paxisim_dist_init_rank.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, P(C.c_void_p)]
-    L.paxisim_dist_allreduce.restype = C.c_int
-    L.paxisim_dist_allreduce.argtypes = [C.c_void_p, P(C.c_uint64), C.c_uint32, P(C.c_double), C.c_uint32,
-                                         P(C.c_uint64), P(C.c_double)]
-    L.paxisim_dist_stats.restype = C.c_int
-    L.paxisim_dist_stats.argtypes = [C.c_void_p, P(abi.Stats), P(C.c_double)]
-    L.paxisim_dist_destroy.restype = C.c_int
-    L.paxisim_dist_destroy.argtypes = [C.c_void_p]
-    L.paxisim_commands.restype = C.c_int
-    L.paxisim_commands.argtypes = [C.c_void_p, C.c_uint64, P(C.c_uint32), C.c_uint32, P(C.c_uint32), P(C.c_uint32)]
-    # client request latency (ABI v14); a library built from older sources (the miscompile guard's
-    # pinned reproducers, __graft_entry__.GUARDS) has none of it, and Simulation.latency* then raise
-    if hasattr(L, "paxisim_latency_enable"):
-        L.paxisim_latency_enable.restype = C.c_int
-        L.paxisim_latency_enable.argtypes = [C.c_void_p, C.c_uint32]
-        L.paxisim_latency_reset.restype = C.c_int
-        L.paxisim_latency_reset.argtypes = [C.c_void_p]
-        L.paxisim_latency_get.restype = C.c_int
-        L.paxisim_latency_get.argtypes = [C.c_void_p, C.c_uint32, P(abi.Latency), P(C.c_uint64)]
-        L.paxisim_latency_stat_of.restype = C.c_int
-        L.paxisim_latency_stat_of.argtypes = [P(abi.Latency), P(C.c_uint64), C.c_double, P(abi.LatencyStat)]
-    # the client-side op history of every protocol (DESIGN.md §3.13): bound where the library has it
-    if hasattr(L, "paxisim_client_history_enable"):
-        L.paxisim_client_history_enable.restype = C.c_int
-        L.paxisim_client_history_enable.argtypes = [C.c_void_p, C.c_uint32]
-        L.paxisim_client_history.restype = C.c_int
-        L.paxisim_client_history.argtypes = [C.c_void_p, C.c_uint64, P(C.c_uint32), C.c_uint32, P(C.c_uint32),
-                                             P(C.c_uint32)]
-        L.paxisim_client_history_load.restype = C.c_int
-        L.paxisim_client_history_load.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, P(C.c_uint32), C.c_uint32]
-        L.paxisim_client_linearizable.restype = C.c_int
-        L.paxisim_client_linearizable.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64), P(C.c_uint64)]
-    # the multi-version Database and Consensus (DESIGN.md §3.14): likewise
-    if hasattr(L, "paxisim_multiversion_enable"):
-        for name, args in abi.MV_PROTOTYPES.items():
-            fn = getattr(L, name)
-            fn.restype = C.c_int
-            fn.argtypes = args
-    # the device message trace (DESIGN.md §3.15): likewise
-    if hasattr(L, "paxisim_trace_enable"):
-        for name, args in abi.TRACE_PROTOTYPES.items():
-            fn = getattr(L, name)
-            fn.restype = C.c_int
-            fn.argtypes = args
-    # snapshot, restore and fork (DESIGN.md §3.16): likewise
-    if hasattr(L, "paxisim_snapshot"):
-        for name, args in abi.SNAPSHOT_PROTOTYPES.items():
-            fn = getattr(L, name)
-            fn.restype = C.c_int
-            fn.argtypes = args
-    # per-cluster verdict words and the search over them (DESIGN.md §3.17): likewise
-    if hasattr(L, "paxisim_verdicts"):
-        for name, args in abi.VERDICT_PROTOTYPES.items():
-            fn = getattr(L, name)
-            fn.restype = C.c_int
-            fn.argtypes = args
-    # which step-kernel unit a handle runs (include/paxisim_shape.h, DESIGN.md §5.20): likewise
-    if hasattr(L, "paxisim_step_unit"):
-        L.paxisim_step_unit.restype = C.c_int
-        L.paxisim_step_unit.argtypes = [C.c_void_p, P(C.c_uint32)]
+    L = abi.bind(C.CDLL(LIB_PATH), "paxisim")
     if L.paxisim_abi_version() != abi.ABI_VERSION:
         raise PaxisimError("ABI version mismatch between paxi_amd/abi.py and libpaxisim.so")
     _lib = L
@@ -141,23 +47,6 @@ def load_library():
 def build_id():
     """The source fingerprint compiled into the loaded library (paxisim_build_id)."""
     return load_library().paxisim_build_id().decode()
-
-
-EXPORTED = ["paxisim_abi_version", "paxisim_build_id", "paxisim_last_error", "paxisim_create", "paxisim_destroy",
-            "paxisim_fault_add", "paxisim_step", "paxisim_sync", "paxisim_stats_get",
-            "paxisim_read_state", "paxisim_read_instances", "paxisim_check", "paxisim_kernel_time", "paxisim_device_bytes",
-            "paxisim_linearizable", "paxisim_history", "paxisim_occupancy", "paxisim_inject", "paxisim_read_log",
-            "paxisim_history_load", "paxisim_active_clusters", "paxisim_read_activity", "paxisim_read_client", "paxisim_quorum", "paxisim_dist_init", "paxisim_dist_unique_id",
-            "paxisim_dist_init_rank", "paxisim_dist_allreduce", "paxisim_dist_stats", "paxisim_dist_destroy",
-            "paxisim_read_kv", "paxisim_read_inbox", "paxisim_deliver", "paxisim_commands",
-            "paxisim_latency_enable", "paxisim_latency_reset", "paxisim_latency_get", "paxisim_latency_stat_of",
-            "paxisim_client_history_enable", "paxisim_client_history", "paxisim_client_history_load",
-            "paxisim_client_linearizable",
-            "paxisim_multiversion_enable", "paxisim_kv_history", "paxisim_consensus", "paxisim_consensus_failed",
-            "paxisim_trace_enable", "paxisim_trace_read", "paxisim_trace_totals",
-            "paxisim_snapshot_size", "paxisim_snapshot", "paxisim_restore", "paxisim_fork", "paxisim_snapshot_info",
-            "paxisim_verdict_available", "paxisim_verdicts", "paxisim_find", "paxisim_verdict_counts",
-            "paxisim_select_words", "paxisim_step_unit"]
 
 
 def consensus_of_histories(histories):
@@ -182,11 +71,11 @@ def _select(fn, n, cap):
     tot = C.c_uint64()
     room = min(n, 1 << 16) if cap is None else min(int(cap), n)
     ids = np.empty(room, dtype=np.uint64)
-    fn(ids.ctypes.data_as(C.c_void_p) if room else None, room, C.byref(tot))
+    fn(ids.ctypes.data_as(_PU64) if room else None, room, C.byref(tot))
     if cap is None and tot.value > room:
         room = tot.value
         ids = np.empty(room, dtype=np.uint64)
-        fn(ids.ctypes.data_as(C.c_void_p), room, C.byref(tot))
+        fn(ids.ctypes.data_as(_PU64), room, C.byref(tot))
     return ids[:min(room, tot.value)], tot.value
 
 
@@ -195,11 +84,9 @@ def select_words(words, any, none=0, cap=None, device=0):
     not words[i] & none, ascending, found on the device: (the first `cap` of them - all when cap is
     None - as a numpy uint64 array, the exact number of matches)."""
     import numpy as np
-    fn = getattr(load_library(), "paxisim_select_words", None)
-    if fn is None:
-        raise PaxisimError(f"{LIB_PATH} was built without paxisim_select_words (verdict words)")
+    fn = load_library().paxisim_select_words
     w = np.ascontiguousarray(words, dtype=np.uint32)
-    ptr = w.ctypes.data_as(C.c_void_p) if w.size else None
+    ptr = w.ctypes.data_as(_PU32) if w.size else None
     return _select(lambda ids, k, tot: _check(fn(device, ptr, w.size, any, none, ids, k, tot)), w.size, cap)
 
 
@@ -208,6 +95,8 @@ def _check(rc):
         raise PaxisimError(f"paxisim error {rc}: {load_library().paxisim_last_error().decode()}")
 
 
+# The two readers below take the call and the error check as arguments: a handle class written
+# outside Handle (a loader of its own around abi.declare) imports them from here.
 def _read_inbox(fn, h, cluster, replica, check):
     n = C.c_uint32()
     cap = 256
@@ -226,21 +115,115 @@ def _read_client(fn, h, cluster, n, check):
     return [arr[i].as_tuple() for i in range(min(n, got.value))]
 
 
-class Simulation:
-    """A batch of independent N-replica clusters on one GPU (one handle)."""
+class Handle:
+    """What a Simulation and the tests' CPU oracle share: a batch of clusters behind one handle of
+    a bound library (abi.Bound, which knows the prefix), with that library's error check.  A
+    subclass sets `_library`, the function that returns its bound library, and `_raise_on`, which
+    raises on a non-zero return code."""
+    _library = staticmethod(load_library)
+    _raise_on = staticmethod(_check)
 
     def __init__(self, cfg, wl, fp=None, faults=()):
-        L = load_library()
         self.cfg, self.wl, self.fp = cfg, wl, fp
         self.N = abi.n_replicas(cfg)
         self.h = C.c_void_p()
-        _check(L.paxisim_create(C.byref(cfg), C.byref(wl), C.byref(fp) if fp else None, C.byref(self.h)))
+        self._raise_on(self._library().create(C.byref(cfg), C.byref(wl), C.byref(fp) if fp else None,
+                                              C.byref(self.h)))
         for f in faults:
             self.fault(f)
 
     # socket.go Drop/Slow/Flaky/Crash, scripted
     def fault(self, f):
-        _check(load_library().paxisim_fault_add(self.h, C.byref(f)))
+        self._raise_on(self._library().fault_add(self.h, C.byref(f)))
+
+    def stats(self):
+        s = abi.Stats()
+        self._raise_on(self._library().stats_get(self.h, C.byref(s)))
+        return s
+
+    def read_state(self, lo=0, n=None):
+        n = self.cfg.clusters - lo if n is None else n
+        arr = (abi.ReplicaState * (n * self.N))()
+        self._raise_on(self._library().read_state(self.h, lo, n, arr))
+        return arr
+
+    def read_instances(self, lo=0, n=None):
+        """Per (cluster, replica, key) Paxos instance state (paxisim_read_instances)."""
+        n = self.cfg.clusters - lo if n is None else n
+        arr = (abi.InstanceState * (n * self.N * abi.n_instances(self.cfg)))()
+        self._raise_on(self._library().read_instances(self.h, lo, n, arr))
+        return arr
+
+    def check(self):
+        v = C.c_uint64()
+        self._raise_on(self._library().check(self.h, C.byref(v)))
+        return v.value
+
+    def inject(self, cluster, replica, cid):
+        """A client request for command `cid` at `replica` in the next step (http.go:99)."""
+        self._raise_on(self._library().inject(self.h, cluster, replica, cid))
+
+    def read_inbox(self, cluster, replica):
+        """Records replica `replica` receives at the next step, by source (paxisim_read_inbox)."""
+        return _read_inbox(self._library().read_inbox, self.h, cluster, replica, self._raise_on)
+
+    def deliver(self, cluster, replica, src, recs):
+        """Append records (src, hdr, ballot, slot, cid) to the replica's next-step
+        inbox from source `src` (paxisim_deliver; a record's own src is ignored)."""
+        arr = (abi.InboxRecord * max(1, len(recs)))(*[abi.InboxRecord(src, *r[-4:]) for r in recs])
+        self._raise_on(self._library().deliver(self.h, cluster, replica, src, arr, len(recs)))
+
+    def read_log(self, cluster, replica, slot_lo, n, key=0):
+        """paxos.go entries of slots [slot_lo, slot_lo+n) of one instance (paxisim_read_log)."""
+        arr = (abi.LogEntry * max(1, n))()
+        self._raise_on(self._library().read_log(self.h, cluster, replica, key, slot_lo, n, arr))
+        return list(arr[:n])
+
+    def history(self, cluster):
+        fn = self._library().history
+        n = C.c_uint32()
+        self._raise_on(fn(self.h, cluster, None, 0, C.byref(n)))
+        buf = (C.c_uint32 * max(1, 5 * n.value))()
+        self._raise_on(fn(self.h, cluster, buf, n.value, C.byref(n)))
+        return [tuple(buf[5 * i: 5 * i + 5]) for i in range(n.value)]
+
+    def read_client(self, cluster):
+        """[(cid, issued, reply_value)] of the cluster's closed-loop workers (paxisim_read_client)."""
+        return _read_client(self._library().read_client, self.h, cluster, self.wl.outstanding, self._raise_on)
+
+    def read_kv(self, cluster, replica, n):
+        """Database.Get (db.go:116-121) of keys [0, n) of one replica (paxisim_read_kv)."""
+        buf = (C.c_uint32 * max(1, n))()
+        self._raise_on(self._library().read_kv(self.h, cluster, replica, buf, n))
+        return list(buf[:n])
+
+    def history_load(self, cluster, replica, ops):
+        """History.ReadFile into the device (paxisim_history_load): ops are
+        (key, is_write, value, start, end) tuples."""
+        flat = [int(v) for o in ops for v in o]
+        buf = (C.c_uint32 * max(1, len(flat)))(*flat)
+        self._raise_on(self._library().history_load(self.h, cluster, replica, buf, len(ops)))
+
+    def close(self):
+        if self.h:
+            self._library().destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Simulation(Handle):
+    """A batch of independent N-replica clusters on one GPU (one handle)."""
 
     def step(self, n):
         _check(load_library().paxisim_step(self.h, n))
@@ -248,46 +231,12 @@ class Simulation:
     def step_unit(self):
         """paxisim_step_unit: the step-kernel unit the next launch runs - abi.UNIT_GENERIC, or
         abi.UNIT_FIXED_PAXOS5 for a handle of the headline's fixed shape (include/paxisim_shape.h)."""
-        fn = getattr(load_library(), "paxisim_step_unit", None)
-        if fn is None:
-            raise PaxisimError(f"{LIB_PATH} was built without paxisim_step_unit")
         u = C.c_uint32()
-        _check(fn(self.h, C.byref(u)))
+        _check(load_library().paxisim_step_unit(self.h, C.byref(u)))
         return u.value
 
     def sync(self):
         _check(load_library().paxisim_sync(self.h))
-
-    def stats(self):
-        s = abi.Stats()
-        _check(load_library().paxisim_stats_get(self.h, C.byref(s)))
-        return s
-
-    def read_state(self, lo=0, n=None):
-        n = self.cfg.clusters - lo if n is None else n
-        arr = (abi.ReplicaState * (n * self.N))()
-        _check(load_library().paxisim_read_state(self.h, lo, n, arr))
-        return arr
-
-    def read_instances(self, lo=0, n=None):
-        """Per (cluster, replica, key) Paxos instance state (paxisim_read_instances)."""
-        n = self.cfg.clusters - lo if n is None else n
-        arr = (abi.InstanceState * (n * self.N * abi.n_instances(self.cfg)))()
-        _check(load_library().paxisim_read_instances(self.h, lo, n, arr))
-        return arr
-
-    def check(self):
-        v = C.c_uint64()
-        _check(load_library().paxisim_check(self.h, C.byref(v)))
-        return v.value
-
-    def inject(self, cluster, replica, cid):
-        """A client request for command `cid` at `replica` in the next step (http.go:99)."""
-        _check(load_library().paxisim_inject(self.h, cluster, replica, cid))
-
-    def read_inbox(self, cluster, replica):
-        """Records replica `replica` receives at the next step, by source (paxisim_read_inbox)."""
-        return _read_inbox(load_library().paxisim_read_inbox, self.h, cluster, replica, _check)
 
     def commands(self, cluster, cids):
         """[(key index, is_write)] of command ids of a cluster (paxisim_commands)."""
@@ -297,47 +246,11 @@ class Simulation:
         _check(load_library().paxisim_commands(self.h, cluster, a, n, k, w))
         return [(k[i], bool(w[i])) for i in range(n)]
 
-    def deliver(self, cluster, replica, src, recs):
-        """Append records (src, hdr, ballot, slot, cid) to the replica's next-step
-        inbox from source `src` (paxisim_deliver; a record's own src is ignored)."""
-        arr = (abi.InboxRecord * max(1, len(recs)))(*[abi.InboxRecord(src, *r[-4:]) for r in recs])
-        _check(load_library().paxisim_deliver(self.h, cluster, replica, src, arr, len(recs)))
-
-    def read_log(self, cluster, replica, slot_lo, n, key=0):
-        """paxos.go entries of slots [slot_lo, slot_lo+n) of one instance (paxisim_read_log)."""
-        arr = (abi.LogEntry * max(1, n))()
-        _check(load_library().paxisim_read_log(self.h, cluster, replica, key, slot_lo, n, arr))
-        return list(arr[:n])
-
     def linearizable(self):
         """History.Linearizable (history.go:55-71): (anomalies, ops checked, partitions skipped)."""
         a, n, sk = C.c_uint64(), C.c_uint64(), C.c_uint64()
         _check(load_library().paxisim_linearizable(self.h, C.byref(a), C.byref(n), C.byref(sk)))
         return a.value, n.value, sk.value
-
-    def history(self, cluster):
-        n = C.c_uint32()
-        _check(load_library().paxisim_history(self.h, cluster, None, 0, C.byref(n)))
-        buf = (C.c_uint32 * max(1, 5 * n.value))()
-        _check(load_library().paxisim_history(self.h, cluster, buf, n.value, C.byref(n)))
-        return [tuple(buf[5 * i: 5 * i + 5]) for i in range(n.value)]
-
-    def read_client(self, cluster):
-        """[(cid, issued, reply_value)] of the cluster's closed-loop workers (paxisim_read_client)."""
-        return _read_client(load_library().paxisim_read_client, self.h, cluster, self.wl.outstanding, _check)
-
-    def read_kv(self, cluster, replica, n):
-        """Database.Get (db.go:116-121) of keys [0, n) of one replica (paxisim_read_kv)."""
-        buf = (C.c_uint32 * max(1, n))()
-        _check(load_library().paxisim_read_kv(self.h, cluster, replica, buf, n))
-        return list(buf[:n])
-
-    def history_load(self, cluster, replica, ops):
-        """History.ReadFile into the device (paxisim_history_load): ops are
-        (key, is_write, value, start, end) tuples."""
-        flat = [int(v) for o in ops for v in o]
-        buf = (C.c_uint32 * max(1, len(flat)))(*flat)
-        _check(load_library().paxisim_history_load(self.h, cluster, replica, buf, len(ops)))
 
     def kernel_time(self, reset=False):
         ms, n = C.c_double(), C.c_uint64()
@@ -370,49 +283,35 @@ class Simulation:
         return b.value
 
     # client request latency (stat.go, benchmark.go:186)
-    @staticmethod
-    def _lat(name):
-        fn = getattr(load_library(), name, None)
-        if fn is None:
-            raise PaxisimError(f"{LIB_PATH} was built without {name} (client request latency, ABI v14)")
-        return fn
-
     def latency_enable(self, bins=256):
         """Record every worker's request latency from now on, in `bins` one-step
         bins (a power of two in [16, abi.LAT_MAX_BINS]); before the first step only."""
-        _check(self._lat("paxisim_latency_enable")(self.h, bins))
+        _check(load_library().paxisim_latency_enable(self.h, bins))
 
     def latency_reset(self):
         """Forget the samples so far (a warm-up); requests in flight keep their issue step."""
-        _check(self._lat("paxisim_latency_reset")(self.h))
+        _check(load_library().paxisim_latency_reset(self.h))
 
     def latency(self, worker=None):
         """The latency.Histogram of one worker, or of all workers (worker=None)."""
         from .latency import Histogram
         lat = abi.Latency()
-        fn = self._lat("paxisim_latency_get")
+        fn = load_library().paxisim_latency_get
         w = abi.ALL_WORKERS if worker is None else worker
         hist = (C.c_uint64 * abi.LAT_MAX_BINS)()
         _check(fn(self.h, w, C.byref(lat), hist))
         return Histogram(hist[:lat.bins], lat.count, lat.sum, lat.overflow, lat.min, lat.max)
 
     # client-side op history of every protocol (benchmark.go:246-275, history.go; DESIGN.md §3.13)
-    @staticmethod
-    def _chist(name):
-        fn = getattr(load_library(), name, None)
-        if fn is None:
-            raise PaxisimError(f"{LIB_PATH} was built without {name} (client-side op history)")
-        return fn
-
     def client_history_enable(self, ops_per_worker):
         """Record every worker's completed ops, `ops_per_worker` per worker and cluster (later ones
         are counted as dropped); once, before the first step and after latency_enable."""
-        _check(self._chist("paxisim_client_history_enable")(self.h, ops_per_worker))
+        _check(load_library().paxisim_client_history_enable(self.h, ops_per_worker))
 
     def client_history(self, cluster):
         """([(key, is_write, value, start, end)] in canonical order - worker 0's ops in completion
         order, then worker 1's, ... -, ops dropped past ops_per_worker) of one cluster."""
-        fn = self._chist("paxisim_client_history")
+        fn = load_library().paxisim_client_history
         n, d = C.c_uint32(), C.c_uint32()
         _check(fn(self.h, cluster, None, 0, C.byref(n), C.byref(d)))
         buf = (C.c_uint32 * max(1, 5 * n.value))()
@@ -424,31 +323,24 @@ class Simulation:
         ops with (key, is_write, value, start, end) tuples."""
         flat = [int(v) for o in ops for v in o]
         buf = (C.c_uint32 * max(1, len(flat)))(*flat)
-        _check(self._chist("paxisim_client_history_load")(self.h, cluster, worker, buf, len(ops)))
+        _check(load_library().paxisim_client_history_load(self.h, cluster, worker, buf, len(ops)))
 
     def client_linearizable(self):
         """History.Linearizable over the client histories: (anomalies, ops checked, partitions skipped)."""
         a, n, sk = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(self._chist("paxisim_client_linearizable")(self.h, C.byref(a), C.byref(n), C.byref(sk)))
+        _check(load_library().paxisim_client_linearizable(self.h, C.byref(a), C.byref(n), C.byref(sk)))
         return a.value, n.value, sk.value
 
     # multi-version Database and Consensus (db.go:123-155, client.go:279-320; DESIGN.md §3.14)
-    @staticmethod
-    def _mv(name):
-        fn = getattr(load_library(), name, None)
-        if fn is None:
-            raise PaxisimError(f"{LIB_PATH} was built without {name} (multi-version Database)")
-        return fn
-
     def multiversion_enable(self, versions_per_key):
         """Keep every replica's History(key): the first `versions_per_key` values put per key (later
         ones are counted as dropped); once, before the first step and after latency_enable."""
-        _check(self._mv("paxisim_multiversion_enable")(self.h, versions_per_key))
+        _check(load_library().paxisim_multiversion_enable(self.h, versions_per_key))
         self._mv_cap = versions_per_key
 
     def kv_history(self, cluster, replica, key):
         """Database.History(key) of one replica: (the values kept, in put order; values dropped)."""
-        fn = self._mv("paxisim_kv_history")
+        fn = load_library().paxisim_kv_history
         cap = getattr(self, "_mv_cap", 0)
         buf = (C.c_uint32 * max(1, cap))()
         n, d = C.c_uint32(), C.c_uint32()
@@ -459,14 +351,14 @@ class Simulation:
         """Consensus over every (cluster, key): (pairs that fail over the kept prefixes, values ever
         put, values dropped)."""
         f, v, d = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(self._mv("paxisim_consensus")(self.h, C.byref(f), C.byref(v), C.byref(d)))
+        _check(load_library().paxisim_consensus(self.h, C.byref(f), C.byref(v), C.byref(d)))
         return f.value, v.value, d.value
 
     def consensus_failed(self, lo=0, n=None):
         """Per cluster of [lo, lo + n): the bit mask of the keys whose Consensus fails."""
         n = self.cfg.clusters - lo if n is None else n
         buf = (C.c_uint64 * max(1, n))()
-        _check(self._mv("paxisim_consensus_failed")(self.h, lo, n, buf))
+        _check(load_library().paxisim_consensus_failed(self.h, lo, n, buf))
         return list(buf[:n])
 
     def consensus_of(self, cluster, key):
@@ -475,26 +367,19 @@ class Simulation:
         return consensus_of_histories([self.kv_history(cluster, r, key)[0] for r in range(self.N)])
 
     # message traces of chosen clusters, recorded on the device
-    @staticmethod
-    def _trace(name):
-        fn = getattr(load_library(), name, None)
-        if fn is None:
-            raise PaxisimError(f"{LIB_PATH} was built without {name} (device message trace)")
-        return fn
-
     def trace_enable(self, clusters, records_per_replica, step_from=0, step_to=2**32 - 1):
         """Record what every replica of the local clusters `clusters` receives at steps [step_from,
         step_to): the first `records_per_replica` records per (cluster, replica), later ones counted
         as dropped; once, before the first step and after latency_enable."""
         clusters = list(clusters)
         arr = (C.c_uint64 * max(1, len(clusters)))(*clusters)
-        _check(self._trace("paxisim_trace_enable")(self.h, arr, len(clusters), records_per_replica, step_from,
+        _check(load_library().paxisim_trace_enable(self.h, arr, len(clusters), records_per_replica, step_from,
                                                    step_to))
 
     def trace_read(self, cluster, replica):
         """([(step, src, hdr, ballot, slot, cid)] one replica of a traced cluster received, by step,
         then source, then FIFO; records dropped past records_per_replica)."""
-        fn = self._trace("paxisim_trace_read")
+        fn = load_library().paxisim_trace_read
         n, d = C.c_uint32(), C.c_uint32()
         _check(fn(self.h, cluster, replica, None, 0, C.byref(n), C.byref(d)))
         arr = (abi.TraceRecord * max(1, n.value))()
@@ -504,21 +389,14 @@ class Simulation:
     def trace_totals(self):
         """(records kept, records dropped) over every traced (cluster, replica)."""
         k, d = C.c_uint64(), C.c_uint64()
-        _check(self._trace("paxisim_trace_totals")(self.h, C.byref(k), C.byref(d)))
+        _check(load_library().paxisim_trace_totals(self.h, C.byref(k), C.byref(d)))
         return k.value, d.value
 
     # snapshot, restore and fork (DESIGN.md §3.16)
-    @staticmethod
-    def _snap(name):
-        fn = getattr(load_library(), name, None)
-        if fn is None:
-            raise PaxisimError(f"{LIB_PATH} was built without {name} (snapshot, restore and fork)")
-        return fn
-
     def snapshot_size(self):
         """The exact size in bytes of a snapshot taken now."""
         n = C.c_uint64()
-        _check(self._snap("paxisim_snapshot_size")(self.h, C.byref(n)))
+        _check(load_library().paxisim_snapshot_size(self.h, C.byref(n)))
         return n.value
 
     def snapshot(self):
@@ -527,7 +405,7 @@ class Simulation:
         import numpy as np
         blob = np.empty(self.snapshot_size(), dtype=np.uint8)
         n = C.c_uint64()
-        _check(self._snap("paxisim_snapshot")(self.h, blob.ctypes.data_as(C.c_void_p), blob.nbytes, C.byref(n)))
+        _check(load_library().paxisim_snapshot(self.h, blob.ctypes.data_as(C.c_void_p), blob.nbytes, C.byref(n)))
         assert n.value == blob.nbytes
         return blob
 
@@ -536,12 +414,12 @@ class Simulation:
         (else PaxisimError, and the handle is unchanged).  Restoring a handle's own snapshot rewinds it."""
         import numpy as np
         blob = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob)
-        _check(self._snap("paxisim_restore")(self.h, blob.ctypes.data_as(C.c_void_p), blob.nbytes))
+        _check(load_library().paxisim_restore(self.h, blob.ctypes.data_as(C.c_void_p), blob.nbytes))
 
     def fork(self):
         """A second, independent Simulation on the same device at the same state (device to device)."""
         h = C.c_void_p()
-        _check(self._snap("paxisim_fork")(self.h, C.byref(h)))
+        _check(load_library().paxisim_fork(self.h, C.byref(h)))
         f = object.__new__(Simulation)
         f.cfg, f.wl, f.fp, f.N, f.h = self.cfg, self.wl, self.fp, self.N, h
         if hasattr(self, "_mv_cap"):
@@ -549,17 +427,10 @@ class Simulation:
         return f
 
     # per-cluster verdict words and the search over them
-    @staticmethod
-    def _verdict(name):
-        fn = getattr(load_library(), name, None)
-        if fn is None:
-            raise PaxisimError(f"{LIB_PATH} was built without {name} (verdict words)")
-        return fn
-
     def verdict_available(self):
         """The abi.V_* / abi.F_* bits this handle can produce."""
         b = C.c_uint32()
-        _check(self._verdict("paxisim_verdict_available")(self.h, C.byref(b)))
+        _check(load_library().paxisim_verdict_available(self.h, C.byref(b)))
         return b.value
 
     def verdicts(self, scans=0, lo=0, n=None):
@@ -568,7 +439,7 @@ class Simulation:
         import numpy as np
         n = self.cfg.clusters - lo if n is None else n
         w = np.empty(max(0, n), dtype=np.uint32)
-        _check(self._verdict("paxisim_verdicts")(self.h, scans, lo, n, w.ctypes.data_as(C.c_void_p) if w.size else None))
+        _check(load_library().paxisim_verdicts(self.h, scans, lo, n, w.ctypes.data_as(_PU32) if w.size else None))
         return w
 
     def find(self, any, none=0, scans=None, cap=None, global_ids=False):
@@ -577,7 +448,7 @@ class Simulation:
         cap is None -, the exact number of matches).  `scans` defaults to the scan bits in any | none;
         ids are local, or with global_ids have cfg.cluster_base added."""
         scans = (any | none) & abi.V_SCANS if scans is None else scans
-        fn = self._verdict("paxisim_find")
+        fn = load_library().paxisim_find
         ids, total = _select(lambda p, k, tot: _check(fn(self.h, scans, any, none, p, k, tot)), self.cfg.clusters, cap)
         if global_ids:
             ids = ids + ids.dtype.type(self.cfg.cluster_base)
@@ -586,25 +457,8 @@ class Simulation:
     def verdict_counts(self, scans=0):
         """{bit name: clusters whose verdict word has the bit} (names: abi.V_NAMES)."""
         c = (C.c_uint64 * 32)()
-        _check(self._verdict("paxisim_verdict_counts")(self.h, scans, c))
+        _check(load_library().paxisim_verdict_counts(self.h, scans, c))
         return {name: c[b] for b, name in abi.V_NAMES.items()}
-
-    def close(self):
-        if self.h:
-            load_library().paxisim_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Dist:

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .sim import PaxisimError, _check, load_library
+from .sim import _check, load_library
 
 
 def _blob(blob):
@@ -21,12 +21,9 @@ def _blob(blob):
 def info(blob):
     """What the blob's header says (paxisim_snapshot_info): protocol, N, clusters, cluster_base,
     step, build id, the recorders present, each section's byte size and mailbox_records."""
-    fn = getattr(load_library(), "paxisim_snapshot_info", None)
-    if fn is None:
-        raise PaxisimError("the library was built without paxisim_snapshot_info")
     b = _blob(blob)
     out = abi.SnapshotInfo()
-    _check(fn(b.ctypes.data_as(C.c_void_p), b.nbytes, C.byref(out)))
+    _check(load_library().paxisim_snapshot_info(b.ctypes.data_as(C.c_void_p), b.nbytes, C.byref(out)))
     return {
         "version": out.version, "protocol": out.protocol, "N": out.n_replicas, "clusters": out.clusters,
         "cluster_base": out.cluster_base, "step": out.step, "build_id": out.build_id.decode(),

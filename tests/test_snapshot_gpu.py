@@ -556,6 +556,9 @@ def test_refusals():
         before = [x.as_tuple() for x in s.read_state()]
         with pytest.raises(_err(), match=msg):
             s.restore(blob[:-16] if msg == "snapshot truncated" else blob)
+        if msg == "snapshot truncated":
+            with pytest.raises(_err(), match=msg):
+                s.restore(blob[:0])                         # an empty buffer
         assert [x.as_tuple() for x in s.read_state()] == before and s.stats().steps == 5, msg
         s.close()
     bad = blob.copy()

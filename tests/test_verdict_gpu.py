@@ -76,6 +76,8 @@ def test_select_words_against_nonzero(n):
     assert total == len(want) and np.array_equal(ids, want), n
     ids, total = select_words(w, 0)                                          # every word
     assert total == n and np.array_equal(ids, np.arange(n)), n
+    ids, total = select_words(w[:0], BIT)                                    # no words: NULL words and ids
+    assert total == 0 and len(ids) == 0 and ids.dtype == np.uint64
 
 
 # ---- 2. Stall triage ---------------------------------------------------------------------------
@@ -111,6 +113,8 @@ def _triage(shape, chunks, ref, frozen=False):
             assert _ids(ids) == stalled and total == len(stalled)
             ids, total = g.find(V.V_STALLED, cap=3)
             assert _ids(ids) == stalled[:3] and total == len(stalled)
+            ids, total = g.find(V.V_STALLED, cap=0)             # NULL ids: the count alone
+            assert len(ids) == 0 and total == len(stalled)
             ids, _ = g.find(V.V_STALLED, global_ids=True)
             assert _ids(ids) == [c + cfg.cluster_base for c in stalled]
         counts = g.verdict_counts()

@@ -8,11 +8,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from paxi_amd import abi
 
-L = C.CDLL(os.path.join(ROOT, "paxi_amd", "libpaxisim_stamps.so"))
-abi.declare(L, "paxisim")
-L.paxisim_step.argtypes = [C.c_void_p, C.c_uint32]
-L.paxisim_dbg_enable.argtypes = [C.c_void_p]
-L.paxisim_dbg_read.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+LIB = os.path.join(ROOT, "paxi_amd", "libpaxisim_stamps.so")
+L = abi.bind(C.CDLL(LIB), "paxisim", {**abi.PROTOTYPES, **abi.DEBUG_PROTOTYPES})
 clusters = int(sys.argv[1])
 cfg = abi.make_config(npz=[5], clusters=clusters, seed=42, window=int(os.environ.get("W", "16")), mbox_cap=16, max_delay=4, steps_per_launch=50)
 wl = abi.make_workload(outstanding=8, target=0)

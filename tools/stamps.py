@@ -10,11 +10,8 @@ sys.path.insert(0, ROOT)
 from paxi_amd import abi
 import bench
 
-L = C.CDLL(os.path.join(ROOT, "paxi_amd", os.environ.get("PAXISIM_STAMPS_LIB", "libpaxisim_stamps.so")))
-abi.declare(L, "paxisim")
-L.paxisim_step.argtypes = [C.c_void_p, C.c_uint32]
-L.paxisim_dbg_enable.argtypes = [C.c_void_p]
-L.paxisim_dbg_read.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+LIB = os.path.join(ROOT, "paxi_amd", os.environ.get("PAXISIM_STAMPS_LIB", "libpaxisim_stamps.so"))
+L = abi.bind(C.CDLL(LIB), "paxisim", {**abi.PROTOTYPES, **abi.DEBUG_PROTOTYPES})
 clusters, warm, steps = (int(a) for a in sys.argv[1:4])
 config = int(sys.argv[4]) if len(sys.argv) > 4 else 2
 args = argparse.Namespace(window=bench.DEFAULTS[config]["window"], mbox=bench.DEFAULTS[config]["mbox"], history=512, kv=1,

@@ -21,7 +21,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from paxi_amd.sim import Simulation, load_library  # noqa: E402
+from paxi_amd import abi  # noqa: E402
+from paxi_amd.sim import LIB_PATH, Simulation  # noqa: E402
 
 # TallyClass (paxisim_dev.h), in order
 CLASSES = ["record load", "record store", "instance load", "instance store", "entry load", "entry store",
@@ -42,9 +43,7 @@ def main():
     a.crash_step = a.warmup * a.sim_steps
     os.environ.setdefault("PAXISIM_LAUNCH_STEPS", str(bench.launch_steps(cfg_id)))
     cfg, wl, fp, faults, _ = bench.workload(cfg_id, clusters, 0, 0, a)
-    L = load_library()
-    L.paxisim_dbg_enable.argtypes = [C.c_void_p]
-    L.paxisim_dbg_read.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+    L = abi.bind(C.CDLL(LIB_PATH), "paxisim", abi.DEBUG_PROTOTYPES)   # the same library Simulation loads
     g = Simulation(cfg, wl, fp, faults)
     for _ in range(a.warmup):
         g.step(a.sim_steps)

@@ -26,12 +26,8 @@ sys.path.insert(0, ROOT)
 from paxi_amd import abi  # noqa: E402
 import bench  # noqa: E402
 
-L = C.CDLL(os.path.join(ROOT, os.environ.get("PAXISIM_WT_LIB", "var/v_wavetimes.so")))
-abi.declare(L, "paxisim")
-L.paxisim_step.argtypes = [C.c_void_p, C.c_uint32]
-L.paxisim_dbg_enable.argtypes = [C.c_void_p]
-L.paxisim_dbg_read.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
-L.paxisim_occupancy.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+LIB = os.path.join(ROOT, os.environ.get("PAXISIM_WT_LIB", "var/v_wavetimes.so"))
+L = abi.bind(C.CDLL(LIB), "paxisim", {**abi.PROTOTYPES, **abi.DEBUG_PROTOTYPES})
 
 
 def main():
